@@ -3,7 +3,7 @@
 distance head + DML loss + SGD), synthetic 768x768 crops, 16 images per GPU (BASELINE.json configs[2];
 configs[3] when launched on 8 ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--batch 16] [--size 768]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--batch 16] [--size 768] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -133,6 +133,40 @@ def synth_batch(batch, size, rank, device):
     lab = torch.randint(0, 16, (batch, size, size), generator=g)
     lab[:, : max(1, size * 38 // 768)] = 255            # ~5 % ignored pixels
     return img.to(device), lab.to(device)
+
+
+DUMP_BUDGET = 60 << 20          # array data; with the .npy headers the directory stays under 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per entry of `arrays` (tensors,
+    numbers or None), float64 where the value is float64 and float32 otherwise, under 64 MB in all.  The smallest arrays
+    are written whole; an array larger than its share of what is left becomes a fixed sample of its flattened elements
+    (indices from a generator seeded with 0, sorted), so two builds given the same arguments can be compared element
+    for element.  What was written (shape, whole or sampled) goes to stderr."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    items = []
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        t = v.detach() if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float64)
+        items.append((name, t.reshape(-1), tuple(t.shape)))
+    items.sort(key=lambda it: it[1].numel())
+    left = DUMP_BUDGET
+    for i, (name, flat, shape) in enumerate(items):
+        dt = torch.float64 if flat.dtype == torch.float64 else torch.float32
+        cap = left // (len(items) - i) // (8 if dt == torch.float64 else 4)
+        if flat.numel() <= cap:
+            a = flat.to(dt).cpu().numpy().reshape(shape)
+        else:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(flat.numel(), (cap,), generator=g).sort().values
+            a = flat[idx.to(flat.device)].to(dt).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        sys.stderr.write("bench.py: %s/%s.npy: %s of %s %s\n" % (dirname, name, "%d sampled elements" % a.size if a.size != flat.numel()
+                                                                   else "all", list(shape), a.dtype))
 
 
 def conv_bytes_of_plan(plan):
@@ -588,6 +622,8 @@ def infer_bench(args):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": preds, "features": score} if fwd_only else {"preds": preds, "score": score})
     roof = None
     if rank == 0 and world == 1 and not args.no_profile:
         # every conv launch of the (un-forked) forward plan alone on the stream, HIP events around each: algorithmic FLOPs / summed time
@@ -657,6 +693,8 @@ def ood_bench(args):
         preds, res = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"preds": preds, "auroc_aupr_fpr": list(res) if res is not None else None})
     print(json.dumps({
         "metric": "images/sec open-set evaluation (5-scale ResNet-50-dilated + PPM embedding decoder, dissum, AUROC/AUPR/FPR95)",
         "value": args.steps / elapsed, "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -692,7 +730,12 @@ def main():
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--print-csrc-sha", action="store_true", help="print the fingerprint of the kernel sources and exit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; float32 / float64, "
+                         "under 64 MB in all: larger outputs as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.print_csrc_sha:
         print(csrc_sha())
         return
@@ -713,7 +756,8 @@ def main():
     backend = dist.get_backend() if dp else None
 
     res = train_pass(args, args.dtype, device, rank, world, steps=args.steps, warmup=args.warmup,
-                     profile=(world == 1 and not args.no_profile), dump_conv=args.dump_conv)
+                     profile=(world == 1 and not args.no_profile), dump_conv=args.dump_conv,
+                     dump_dir=args.dump_outputs if rank == 0 else None)
     out = None
     if rank == 0:
         out = {"metric": "images/sec train-step, DeepLabV3+R101 768x768 bs=16; % HBM & MFMA roofline",
@@ -787,9 +831,10 @@ def main():
         dist.destroy_process_group()
 
 
-def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_conv=None):
+def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_conv=None, dump_dir=None):
     """W warm-up + exactly K timed train steps in `dtype` (barrier + synchronize on both sides, max over ranks), then --
-    single GPU only -- the profiled conv pass.  The model and its plans are released on return."""
+    single GPU only -- the profiled conv pass.  `dump_dir`: the last timed step's loss, logits, prototypes, features and the
+    model state after its optimizer step go there (dump_outputs).  The model and its plans are released on return."""
     from dmlnet import parallel
     import network
     import utils
@@ -815,13 +860,15 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         model._engine.reducer = parallel.GradReducer(model._engine.store, bucket_mb=32.0, average=False)
     img, lab = synth_batch(args.batch, args.size, rank, device)
 
-    def step():
+    def step(keep=None):
         opt.zero_grad()
         logits, centers, feats = model(img)
         loss = crit(logits, lab, feats)
         loss.backward()
         opt.step()
         sched.step()
+        if keep is not None:
+            keep.update(loss=loss, logits=logits, centers=centers, features=feats)
         return loss
 
     for _ in range(warmup):
@@ -849,9 +896,10 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         del buf
         dist.barrier()
     torch.cuda.synchronize()
+    last = {} if dump_dir else None
     t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = step()
+    for i in range(steps):
+        loss = step(last if i == steps - 1 else None)
     torch.cuda.synchronize()
     if dp:
         dist.barrier()
@@ -862,6 +910,10 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     final_loss = float(loss.item())
+    if dump_dir:
+        last["state"] = torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()])
+        dump_outputs(dump_dir, last)
+        del last
     # host time to ENQUEUE one step (outside the timed region): the queue is drained first, so the launches never wait
     # for the GPU and what is measured is the host's own work (Python + the native launch-list replay + HIP launches)
     host = 0.0
