@@ -492,9 +492,11 @@ class Plan:
         return lst
 
     # ---- fp32 plans with fp32_products = "f16x2": fp16 hi / lo planes of a conv operand (DmlConvDesc.x_planes)
-    def h2_ok(self, C, N, taps):
-        """shapes the planes kernel takes (conv_ws_planes_eligible); the others run the three-term split on the fp32 tensors"""
-        return self.f32_split == 2 and self.dtype == torch.float32 and C % 32 == 0 and N % 64 == 0 and taps <= 32
+    def h2_ok(self, C, N, taps, dgrad=False):
+        """shapes the planes kernel takes (conv_ws_planes_eligible); the others run the three-term split on the fp32 tensors.
+        dgrad: a data-gradient launch (mode 1), whose K = taps x C must be at least two K stages (2 x BK = 64)"""
+        return (self.f32_split == 2 and self.dtype == torch.float32 and C % 32 == 0 and N % 64 == 0 and taps <= 32
+                and (not dgrad or taps * C >= 64))
 
     @staticmethod
     def planes_fit(M, ld):
@@ -570,7 +572,7 @@ class Plan:
     def set_planes(self, dsc, x: Act, w, rows, K, ops):
         """DmlConvDesc.f32_split / x_planes / w_planes of a conv of this plan reading activation x and weight copy w[rows][K]"""
         dsc.f32_split = min(self.f32_split, 1)
-        if self.h2_ok(x.C, rows, dsc.R * dsc.S):
+        if self.h2_ok(x.C, rows, dsc.R * dsc.S, dgrad=dsc.mode == 1):
             dsc.f32_split = 2
             dsc.x_planes, dsc.x_plane_stride, dsc.x_unscale = self.h2_of(x, ops)
             dsc.w_planes, dsc.w_plane_stride, dsc.w_unscale = self.h2_weight(w, rows, K)
@@ -686,6 +688,10 @@ class Plan:
                 and self.f32_split == 2 and self.dtype == torch.float32 and not isinstance(conv, _S2DConv)):
             return False
         if x is not x.root or x.g32 is not None or x.H != 2 * dy.H or x.W != 2 * dy.W or dy.C % 32 or x.C % 64:
+            return False
+        # every class is a launch of the planes kernel, whose data gradients need K = taps x dy.C >= 2 x BK = 64
+        # (conv_ws_planes_eligible); the smallest class has one tap (3x3: odd rows and columns, 1x1: the even pixels)
+        if dy.C < 64:
             return False
         if kh == 1 and not x.root.grad_init:
             return False
@@ -959,7 +965,7 @@ class Plan:
         gwork = None
         if dy_direct:
             only = (u.x.C % 8 == 0 and self.planes_fit(M, N) and self.planes_fit(u.x.root.M, u.x.root.ld)
-                    and (not need_dgrad or self.h2_ok(N, u.x.C, kh * kw)))
+                    and (not need_dgrad or self.h2_ok(N, u.x.C, kh * kw, dgrad=True)))
             dy = self.h2_direct(u.y.B, u.y.H, u.y.W, N, fp32_too=not only)
             gwork = self.h2_work()
         else:
@@ -1099,7 +1105,7 @@ class Plan:
                    # its memory instructions.  With the masks of a sub-tile in one 16-byte load per row, conv_epilogue_rows, it wins:
                    # 187.6 -> 190.1 images/s, three interleaved rounds, profiles/r05_ab_maskvec_res.txt; without the fusion that
                    # change alone is +0.3 %.)  DML_FUSE_RES_GRAD=0: off
-                   or (self.h2_direct_on and self.h2_ok(u1.conv.out_channels, xb.C, 1) and xb.C % 64 == 0
+                   or (self.h2_direct_on and self.h2_ok(u1.conv.out_channels, xb.C, 1, dgrad=True) and xb.C % 64 == 0
                        and self.planes_fit(u1.y.M, u1.conv.out_channels)))):
             # The masked output gradient is this block's contribution to d(xb) through the identity branch.  Instead
             # of having the BN-backward apply write that copy (75 MB per layer3 block) for conv1's data gradient to
@@ -1811,13 +1817,16 @@ class Engine:
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("expected input [B,3,H,W], got %s" % (tuple(x.shape),))
         synced = bool(self.sync_bn and dist.is_available() and dist.is_initialized() and dist.get_world_size(self.sync_group) > 1)
-        if training and x.shape[0] < 2 and not synced and self.bn_modes() != (1 << len(self._bn_list)) - 1:
-            # same failure as the reference: BatchNorm over B x 256 x 1 x 1 in ASPPPooling (network/utils.py:318-329)
-            # (synchronised statistics span the ranks: one image per rank is a legal batch there)
-            raise ValueError("Expected more than 1 value per channel when training, got input size "
-                             "torch.Size([%d, 256, 1, 1])" % x.shape[0])
         x = x.contiguous().float()
         plan = self.plan_for(x, dtype, training)
+        if training and x.shape[0] < 2 and not synced:
+            for u in plan.units:
+                if u.bn.training and u.y.M < 2:
+                    # same failure as the reference: a batch-statistics BatchNorm over one value per channel -- at batch 1 the
+                    # one of ASPPPooling (network/utils.py:318-329), unless it runs on its running statistics (eval())
+                    # (synchronised statistics span the ranks: one image per rank is a legal batch there)
+                    raise ValueError("Expected more than 1 value per channel when training, got input size "
+                                     "torch.Size([%d, %d, %d, %d])" % (u.y.B, u.bn.num_features, u.y.H, u.y.W))
         stream = torch.cuda.current_stream(x.device).cuda_stream
         plan.refresh_weights(stream, overlap=training)
         B, _, H, W = x.shape

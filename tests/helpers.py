@@ -130,12 +130,15 @@ def max_abs(a, b) -> float:
 # block_bwd / _head_fwd / _head_bwd), so that the per-block and head-only fixtures (G4, G3: SURVEY 8(c) calls them "the
 # binding fixtures") bind the HIP path and not only the oracle
 # ---------------------------------------------------------------------------------------------------
-def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float32):
+def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float32, products=None):
     """kind = "block": module is a network.modeling.Bottleneck, in_shapes = [(B, C, H, W)];
     kind = "head": module is a network.modeling.DeepLabHeadV3Plus, in_shapes = [low (B,256,h,w), out (B,2048,h',w')].
+    products: the fp32 plan's convolution products ("exact", "bf16x3", "f16x2", as model.set_compute_dtype's fp32_products);
+    None = the engine's default.
     Returns a PiecePlan with .run(inputs, grad_out) -> (output, input gradients); parameter gradients / running
     statistics land in the module (p.grad, buffers) exactly as in the full model."""
     import torch.nn as nn
+    from dmlnet import _lib
     from dmlnet import engine as E
 
     class _Holder(nn.Module):
@@ -148,10 +151,17 @@ def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float3
         def build(self):
             self.bn_eval, self.pre_prep, self.nbt_inc = [], [], None
             self.to_backbone_ops, self.head_bwd_range = [], {}
+            # the head of Plan.build's forward in f16x2 training plans: zero every amax word, one launch for the plane scales of
+            # the residual-free BatchNorm outputs (its table is filled in once the forward is built)
+            self.h2_bound_tab, self.h2_bound_args = [], None
+            if self.h2_slots is not None and self.training:
+                self.call(self.fwd, self.lib.dml_fill_f32, self.h2_slots.data_ptr(), self.h2_slots.numel(), 0.0)
+                self.h2_bound_args = self.call(self.fwd, self.lib.dml_h2_bound_bn_table, 0, 0)
             if kind == "block":
                 B, Cc, Hh, Ww = in_shapes[0]
                 self.inputs = [self.new(B, Hh, Ww, Cc)]
                 rec = self.block_fwd(self.inputs[0], module)
+                self._bound_table()
                 self.output = rec[3].z
                 self.grad_out = self.grad_of(self.output)
                 self.output.root.grad_init = True
@@ -164,12 +174,19 @@ def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float3
                 self.inputs = [low, out]
                 rec = self._head_fwd(module, low, out)
                 self.heads = [rec]
+                self._bound_table()
                 self.n_fwd = len(self.fwd) - 1              # without the final upsample + distance op (needs per-call outputs)
                 self.output = rec.emb
                 self._head_bwd(rec, low, out)
                 self.flush_wgrad()
                 self.grad_out = rec.de
                 self.skip = [r for r in (rec.fused_range, rec.unfused_range) if r is not None]
+
+        def _bound_table(self):
+            if self.h2_bound_args is not None and self.h2_bound_tab:
+                arr = (_lib.H2BoundDesc * len(self.h2_bound_tab))(*self.h2_bound_tab)
+                self.h2_bound_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+                self.h2_bound_args[0], self.h2_bound_args[1] = self.h2_bound_table.data_ptr(), len(self.h2_bound_tab)
 
         @staticmethod
         def _fill(act, t):          # NCHW cpu tensor -> the plan's NHWC buffer
@@ -201,6 +218,8 @@ def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float3
 
     holder = _Holder().cuda()
     eng = E.Engine(holder)
+    if products is not None:
+        eng.f32_split = {"exact": 0, "bf16x3": 1, "f16x2": 2}[products]
     eng.store.bind(torch.device("cuda", torch.cuda.current_device()))
     (B, _, Hh, Ww) = in_shapes[0]
     H_full, W_full = (Hh, Ww) if kind == "block" else (4 * Hh, 4 * Ww)

@@ -2,6 +2,7 @@
 reference (G5, G5b, G8) and against the CPU oracle on fresh seeded inputs.  Tolerance from BASELINE.json:
 1e-3 (relative to the tensor's max magnitude) in fp32 mode.
 """
+import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
@@ -69,9 +70,13 @@ def test_g5l_full_train_step_matches_reference(products):
     noise) of zero, so no summation order can flip a mask (tests/tools/mint_golden_large.py).  Logits, loss, running statistics at
     1e-3; all 338 parameter-gradient checksums and the sampled gradients at 1e-3 as well (the 64 x 64 fixture needed 2e-3;
     measured here: 5e-5 .. 8e-5 in every mode, the reference's own fp32-vs-fp64 checksum noise is 3e-5)."""
+    _g5l_step_matches_reference(build(fp32_products=products, state=conditioned("g5l_full_train", 1)), products)
+
+
+def _g5l_step_matches_reference(m, products):
+    """the assertions of test_g5l_full_train_step_matches_reference on a built model `m` (one train step); returns `m`"""
     import utils
     g = H.load_golden("g5l_full_train")
-    m = build(fp32_products=products, state=conditioned("g5l_full_train", 1))
     img, lab = g5l_inputs()
     lg, ctr, ft = m(img)
     assert lg.shape == (2, 16, 128, 128) and ft.shape == (2, 128, 128, 16) and ctr.shape == (16, 16)
@@ -100,6 +105,7 @@ def test_g5l_full_train_step_matches_reference(products):
     relclose(bufs["backbone.layer4.2.bn3.running_var"], T(g["rv_l4"]), TOL, "running_var layer4")
     relclose(bufs["classifier.classifier.1.running_var"], T(g["rv_head"]), TOL, "running_var head")
     assert int(bufs["backbone.bn1.num_batches_tracked"]) == 1
+    return m
 
 
 def test_g5_full_train_step_matches_reference():
@@ -181,6 +187,11 @@ def test_g8l_sgd_polylr_trajectory(products):
     reference's trajectory.  The bars are the FIXTURE's, one rule for every mode: at step t, 8 x the largest deviation (steps <= t)
     between the reference's own fp32 / 8 threads, fp32 / 1 thread and fp64 runs, floor 1e-5 (tests/tools/mint_golden_large.py) --
     the weights of steps 1.. are the optimizer's and cannot be conditioned, so the reference's own run-to-run spread is the yardstick."""
+    _g8l_trajectory_matches_reference(products)
+
+
+def _g8l_trajectory_matches_reference(products):
+    """the six steps and assertions of test_g8l_sgd_polylr_trajectory; returns the model"""
     import utils
     from dmlnet.optim import FusedSGD
     t = H.load_golden("g8l_trajectory")
@@ -211,6 +222,7 @@ def test_g8l_sgd_polylr_trajectory(products):
         got = got if got.numel() < 70000 else got.contiguous().flatten()[::61]
         ref = T(t["w_%d" % i])
         relclose(got.reshape(ref.shape), ref, float(bar), "%s after 6 steps" % k)
+    return m
 
 
 def test_g8_sgd_polylr_trajectory():
@@ -961,6 +973,225 @@ def test_g4_bottleneck_fixture_through_the_hip_plan(name, cfg):
     for k, b in blk.named_buffers():
         if "num_batches" not in k:
             relclose(b, T(g[name + "_buf__" + k.replace(".", "_")]), TOL, k)
+
+
+EPS32 = float(np.finfo(np.float32).eps)
+RELU_MARGIN = 64.0          # |ReLU input| >= 64 x eps32 x sum|terms| (tests/tools/mint_golden_large.py: FACT)
+
+
+def _block64(blk, x, w=None):
+    """fp64 train-mode forward (and backward with output gradient `w`) of a Bottleneck (resnet.py:95-115) on a float64 copy, and
+    per ReLU (z1, z2, z3): the input and eps32 x sum|terms| of it (the bound of any fp32 rounding of that value, as
+    tests/tools/mint_golden_large.py measures it)."""
+    import copy
+    import torch.nn.functional as F
+    b = copy.deepcopy(blk).double().train()
+    x = x.double().requires_grad_(w is not None)
+
+    def unit(conv, bn, inp):
+        y = conv(inp)
+        with torch.no_grad():
+            ya = F.conv2d(inp.detach().abs(), conv.weight.abs(), None, conv.stride, conv.padding, conv.dilation)
+            yd = y.detach()
+            mean = yd.mean((0, 2, 3), keepdim=True)
+            inv = (yd.var((0, 2, 3), unbiased=False, keepdim=True) + bn.eps).rsqrt()
+            terms = bn.weight.abs().view(1, -1, 1, 1) * inv * (ya + mean.abs()) + bn.bias.abs().view(1, -1, 1, 1)
+        return bn(y), terms
+
+    z1, t1 = unit(b.conv1, b.bn1, x)
+    z2, t2 = unit(b.conv2, b.bn2, F.relu(z1))
+    z3, t3 = unit(b.conv3, b.bn3, F.relu(z2))
+    if b.downsample is not None:
+        idt, td = unit(b.downsample[0], b.downsample[1], x)
+    else:
+        idt, td = x, x.detach().abs()
+    z3 = z3 + idt
+    out = F.relu(z3)
+    if w is not None:
+        out.backward(w.double())
+    relus = [(z.detach(), EPS32 * (t + (td if i == 2 else 0))) for i, (z, t) in enumerate(((z1, t1), (z2, t2), (z3, t3)))]
+    return b, x, out.detach(), relus
+
+
+def _clear_relu_edges(blk, x):
+    """Move the BatchNorm betas of the channels with a ReLU input inside RELU_MARGIN x eps32 x sum|terms| of zero (the way
+    mint_golden_large.py conditions its fixtures, deterministically): each such channel shifts so that zero sits in the middle of the
+    nearest gap of its values wide enough to clear both neighbours.  bn1, bn2, bn3 in turn, each after the fp64 forward of the betas moved so far."""
+    for i, bn in enumerate((blk.bn1, blk.bn2, blk.bn3)):
+        z, unit = _block64(blk, x)[3][i]
+        band = 1.5 * RELU_MARGIN * unit
+        bad = (z.abs() < band).transpose(0, 1).flatten(1).any(1).nonzero().flatten().tolist()
+        for c in bad:
+            v, bd = z[:, c].flatten(), band[:, c].flatten()
+            order = v.argsort()
+            v, bd = v[order], bd[order]
+            lo, hi = v[:-1] + bd[:-1], v[1:] - bd[1:]              # -shift in (lo, hi): the gap between two values clears both
+            mid = 0.5 * (lo + hi)[hi > lo]
+            shift = -mid[mid.abs().argmin()].item()
+            with torch.no_grad():
+                bn.bias[c] += shift
+    return min(float((z.abs() / unit).min()) for z, unit in _block64(blk, x)[3])
+
+
+BOTTLENECK_SWEEP = [      # (inplanes, planes, stride, dilation, downsample, H, W)
+    ("64-16-s1", (64, 16, 1, 1, False, 16, 16)),
+    ("256-64-s1-odd", (256, 64, 1, 1, False, 15, 17)),
+    ("64-8-s2-ds", (64, 8, 2, 1, True, 16, 16)),           # downsample data gradient: dy.C = 32, its one-tap class K = 32
+    ("128-32-s2-ds", (128, 32, 2, 1, True, 16, 16)),       # conv2's data gradient on 32 channels
+    ("256-64-s2-ds", (256, 64, 2, 1, True, 16, 16)),       # one-tap class K = 64 = 2 x BK
+    ("256-64-s2-ds-odd", (256, 64, 2, 1, True, 15, 17)),   # odd map: the direct stride-2 launch
+    ("512-128-s2-ds", (512, 128, 2, 1, True, 24, 24)),
+    ("1024-256-d2", (1024, 256, 1, 2, False, 12, 12)),
+    ("1024-512-d2-ds", (1024, 512, 1, 2, True, 12, 12)),   # OS16 layer4.0: stride-1 downsample
+]
+
+
+@pytest.mark.parametrize("products", ["exact", "bf16x3", "f16x2"])
+@pytest.mark.parametrize("name,cfg", BOTTLENECK_SWEEP, ids=[n for n, _ in BOTTLENECK_SWEEP])
+def test_bottleneck_sweep_through_the_hip_plan(name, cfg, products):
+    """One Bottleneck through the plan's own block pieces (Plan.block_fwd / block_bwd) in each fp32 arithmetic mode, at widths, strides,
+    dilations and map sizes where the f16x2 plan's eligibility rules (h2_ok, s2_classes_ok, planes-only tensors, the three-term
+    fallback) choose different kernels -- against a float64 copy of the same block: output, input gradient, every parameter gradient
+    and the running statistics at G4's bars.  Weights are helpers.synth_state_dict's; BatchNorm betas are moved off the ReLU knife edges
+    (_clear_relu_edges) and the smallest margin is asserted before the HIP run, so no summation order can flip a mask.
+    64-8-s2-ds in f16x2 built a plan that failed at replay with DML_EUNSUPPORTED until s2_classes_ok / h2_ok followed the kernel's
+    K >= 2 x BK rule for data gradients.  Measured: output and d x within 2e-6 of the float64 block in every case and mode."""
+    import torch.nn as nn
+    import network.modeling as NM
+    cin, planes, stride, dil, has_ds, Hh, Ww = cfg
+    torch.manual_seed(0)
+    ds = nn.Sequential(nn.Conv2d(cin, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4)) if has_ds else None
+    blk = NM.Bottleneck(cin, planes, stride, dil, ds)
+    shapes = OrderedDict(("backbone.blk." + k, tuple(v.shape)) for k, v in blk.state_dict().items())
+    sd = H.synth_state_dict(shapes, seed=41)
+    blk.load_state_dict(OrderedDict((k[len("backbone.blk."):], v) for k, v in sd.items()))
+    blk.train()
+    x = H.synth_tensor(41, "sweep.x." + name, (2, cin, Hh, Ww))
+    margin = _clear_relu_edges(blk, x)
+    assert margin >= RELU_MARGIN, "%s: a ReLU input within %.1f x eps32 x sum|terms| of zero" % (name, margin)
+    Ho, Wo = (Hh - 1) // stride + 1, (Ww - 1) // stride + 1
+    w = H.synth_tensor(41, "sweep.w." + name, (2, planes * 4, Ho, Wo))
+    ref, xr, y64, _ = _block64(blk, x, w)
+    blk.cuda()
+    plan = H.piece_plan("block", blk, [tuple(x.shape)], products=products)
+    assert plan.f32_split == {"exact": 0, "bf16x3": 1, "f16x2": 2}[products]
+    y, (dx,) = plan.run([x], w)
+    print("%s %s: margin %.0f, output %.2e, dx %.2e" % (name, products, margin, H.rel_err(y, y64), H.rel_err(dx, xr.grad)))
+    relclose(y, y64, TOL, "block output")
+    relclose(dx, xr.grad, TOL, "d x")
+    rp = dict(ref.named_parameters())
+    for k, p in blk.named_parameters():
+        relclose(p.grad, rp[k].grad, 2 * TOL, "grad " + k)
+    rb = dict(ref.named_buffers())
+    for k, b in blk.named_buffers():
+        if "num_batches" not in k:
+            relclose(b, rb[k], TOL, k)
+
+
+PLAN_SWITCHES = ["DML_H2_DIRECT", "DML_FUSE_RES_GRAD", "DML_RES_PLANES", "DML_FUSE_BN_REDUCE", "DML_FUSE_BOUND", "DML_S2_CLASSES",
+                 "DML_PREP_OVERLAP", "DML_DS_GRAD_FROM_DZ", "DML_BNR_INC", "DML_CAT_PLANES", "DML_STEM_S2D", "DML_GROUP_WGRAD",
+                 "DML_OVERLAP_WGRAD", "DML_NATIVE_PLAN"]
+RUNTIME_SWITCHES = ("DML_PREP_OVERLAP", "DML_OVERLAP_WGRAD", "DML_NATIVE_PLAN")        # act when a plan runs, across steps
+
+
+def _plan_signature(plan):
+    """what a plan launches: per op its function, which arguments are None, and the non-pointer fields (pointer fields: set or not)
+    of a descriptor it takes by reference; with the bytes the plan holds and its weight-preparation work"""
+    def op(fn, args):
+        sig = [getattr(fn, "__name__", "py"), tuple(a is None for a in args)]
+        for a in args:
+            st = getattr(a, "_obj", None)
+            if isinstance(st, C.Structure):
+                sig.append(tuple(bool(getattr(st, f)) if t is C.c_void_p else getattr(st, f) for f, t, *_ in st._fields_))
+        return tuple(sig)
+    return (plan.bytes, len(plan.prep), len(plan.prep_h2), len(plan.prep_gather),
+            tuple(op(f, a) for f, a in plan.fwd), tuple(op(f, a) for f, a in plan.bwd))
+
+
+def _run_observed(monkeypatch, run):
+    """run(): builds and trains a model.  Returns its plan and what its replays did: `side` -- a backward replay was given the side
+    stream (weight gradients beside the data gradients), `split` -- a forward replay stopped at Plan.prep_cut to wait for the weight
+    copies made on the side stream (refresh_weights, overlap)"""
+    from dmlnet import engine as E
+    seen = {"side": False, "split": False}
+    orig = E.Plan._exec
+
+    def rec(self, ops, stream, *a, **kw):
+        if ops is self.bwd and kw.get("side_stream") is not None:
+            seen["side"] = True
+        stop = a[1] if len(a) > 1 else kw.get("stop")
+        if ops is self.fwd and self.prep_cut is not None and stop == self.prep_cut[0]:
+            seen["split"] = True
+        return orig(self, ops, stream, *a, **kw)
+
+    monkeypatch.setattr(E.Plan, "_exec", rec)
+    m = run()
+    monkeypatch.setattr(E.Plan, "_exec", orig)
+    plans = list(m._engine.plans.values())
+    assert len(plans) == 1
+    return plans[0], seen
+
+
+def _launches(sig, name):
+    return sum(1 for ops in sig[4:] for op in ops if op[0] == name)
+
+
+_DEFAULT_F16X2 = {}
+
+
+def _default_f16x2_plan(monkeypatch):
+    """signature and replay of the default f16x2 g5l plan (one step)"""
+    if not _DEFAULT_F16X2:
+        for sw in PLAN_SWITCHES:
+            monkeypatch.delenv(sw, raising=False)
+        plan, seen = _run_observed(monkeypatch, lambda: _g5l_step_matches_reference(
+            build(fp32_products="f16x2", state=conditioned("g5l_full_train", 1)), "f16x2"))
+        _DEFAULT_F16X2.update(sig=_plan_signature(plan), native=bool(plan._nat), **seen)
+    return _DEFAULT_F16X2
+
+
+def _bf16_plan_signature():
+    m = build(dtype=torch.bfloat16, state=conditioned("g5l_full_train", 1))
+    m(g5l_inputs()[0])
+    return _plan_signature(next(iter(m._engine.plans.values())))
+
+
+@pytest.mark.parametrize("switch", PLAN_SWITCHES + ["all"])
+def test_g5l_f16x2_with_a_plan_switch_off(switch, monkeypatch):
+    """The f16x2 training plan with one of its structure switches off (or all of them) against the g5l golden at the bars of
+    test_g5l_full_train_step_matches_reference (_g5l_step_matches_reference, unchanged).  Each switch must change what the plan does:
+    the launches it builds (_plan_signature) or, for the three that act when a plan runs, the forward's wait for the overlapped weight
+    preparation, the native launch lists (Plan._nat) or the backward's side stream -- a switch that silently stops applying fails.
+    DML_GROUP_WGRAD groups bf16 weight gradients only (dml_conv_wgrad_group_eligible): an f16x2 plan has no grouped launch to turn
+    off, which is asserted, and the switch's effect is asserted on the bf16 plan of the same model and input."""
+    default = _default_f16x2_plan(monkeypatch)
+    off = PLAN_SWITCHES if switch == "all" else [switch]
+    bf16_on = _bf16_plan_signature() if switch == "DML_GROUP_WGRAD" else None
+    for sw in off:
+        monkeypatch.setenv(sw, "0")
+    plan, seen = _run_observed(monkeypatch, lambda: _g5l_step_matches_reference(
+        build(fp32_products="f16x2", state=conditioned("g5l_full_train", 1)), "f16x2 %s=0" % switch))
+    assert plan.f32_split == 2
+    sig = _plan_signature(plan)
+    changed = {"plan": sig != default["sig"], "DML_PREP_OVERLAP": default["split"] and not seen["split"],
+               "DML_NATIVE_PLAN": default["native"] and not plan._nat, "DML_OVERLAP_WGRAD": default["side"] and not seen["side"]}
+    if bf16_on is not None:
+        bf16_off = _bf16_plan_signature()
+        changed["DML_GROUP_WGRAD"] = (_launches(default["sig"], "dml_conv_wgrad_group") == 0 and
+                                      _launches(bf16_on, "dml_conv_wgrad_group") > 0 and _launches(bf16_off, "dml_conv_wgrad_group") == 0)
+    for sw in off:
+        key = sw if sw in changed else "plan"
+        assert changed[key], "%s=0 did not change the plan or its replay" % sw
+
+
+@pytest.mark.parametrize("switch", RUNTIME_SWITCHES)
+def test_g8l_f16x2_trajectory_with_a_runtime_switch_off(switch, monkeypatch):
+    """The switches that act across steps (weights prepared again after every optimizer step, on the side stream or not; the launch
+    lists replayed natively or from Python; weight gradients on the side stream or not): the six-step g8l trajectory in f16x2 with the
+    switch off, at the fixture's stored bars (_g8l_trajectory_matches_reference, unchanged)."""
+    monkeypatch.setenv(switch, "0")
+    plan, seen = _run_observed(monkeypatch, lambda: _g8l_trajectory_matches_reference("f16x2"))
+    assert {"DML_PREP_OVERLAP": not seen["split"], "DML_NATIVE_PLAN": not plan._nat, "DML_OVERLAP_WGRAD": not seen["side"]}[switch]
 
 
 @pytest.mark.parametrize("both", [True, False])

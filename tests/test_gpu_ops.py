@@ -1677,6 +1677,39 @@ def test_stride2_data_gradient_by_parity_class_equals_the_direct_launch(lib, cas
     assert lib.dml_conv_igemm(C.byref(d), st()) == -1                # forward launches have no sub-grid: DML_EINVAL
 
 
+@pytest.mark.parametrize("Cout,ok", [(32, False), (64, True)])
+def test_sub_grid_class_with_k_below_two_stages_is_refused(lib, Cout, ok):
+    """A parity-class launch (DmlConvDesc.sub_grid) exists on the planes kernel only, whose data gradients need K = taps x C of at
+    least two K stages (2 x BK = 64).  The 1x1 stride-2 class on dY of 32 channels has K = 32: DML_EUNSUPPORTED, nothing written (the
+    plan must not build it: Plan.s2_classes_ok).  Dy of 64 channels, same geometry, is taken and equals the fp64 data gradient on the
+    even pixels."""
+    from dmlnet._lib import ConvDesc
+    B, Ho, Wo, Cin = 2, 6, 5, 64
+    Hh, Ww = 2 * Ho, 2 * Wo
+    gy = torch.randn(B, Ho, Wo, Cout, device="cuda") * 1e-2
+    w = torch.randn(Cout, Cin, device="cuda") * (2.0 / Cin) ** 0.5
+    sub = w.t().contiguous()                                   # [Cin][1 tap x Cout]: the class's operand
+    yp, yw = h2_planes(lib, gy.view(-1, Cout), 0)
+    wp, ww = h2_planes(lib, sub, 1)
+    old = torch.randn(B, Hh, Ww, Cin, device="cuda") * 1e-3
+    dx = old.clone()
+    d = ConvDesc(x=gy.data_ptr(), w=sub.data_ptr(), y=dx.data_ptr(), bias=None, stats=None, B=B, Hi=Ho, Wi=Wo, C=Cout, ldx=Cout,
+                 Ho=Ho, Wo=Wo, N=Cin, ldy=Cin, R=1, S=1, stride=1, dil=1, pad=0, dtype=0, y_f32=0, accum=1, mode=1)
+    d.pad_w_set, d.pad_w, d.sub_grid, d.sub_y, d.sub_x, d.f32_split, d.ws_min_tiles = 1, 0, 1, 0, 0, 2, 1
+    d.x_planes, d.x_unscale, d.x_plane_stride = yp.data_ptr(), yw.data_ptr() + 4096, yp.shape[1]
+    d.w_planes, d.w_unscale, d.w_plane_stride = wp.data_ptr(), ww.data_ptr() + 4096, wp.shape[1]
+    rc = lib.dml_conv_igemm(C.byref(d), st())
+    torch.cuda.synchronize()
+    if not ok:
+        assert rc == -3                                        # DML_EUNSUPPORTED
+        assert torch.equal(dx, old)
+        return
+    chk(rc)
+    ref = old.double().clone()
+    ref[:, ::2, ::2] += (gy.double().view(-1, Cout) @ w.double()).view(B, Ho, Wo, Cin)
+    assert (dx.double() - ref).abs().max().item() <= 1e-5 * ref.abs().max().item()
+
+
 def test_planes_only_operand_is_refused_where_the_planes_kernels_cannot_take_it(lib):
     """x == x_planes (dy == dy_planes) declares an operand that exists as fp16 planes ONLY (the plan drops the fp32 copy of tensors only
     convolutions read).  A launch the planes kernels cannot take must then fail with DML_EUNSUPPORTED -- the fallback kernels would read

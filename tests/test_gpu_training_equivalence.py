@@ -210,12 +210,45 @@ def test_bf16_training_tracks_fp32_over_30_steps():
     assert not bad, bad
 
 
-def test_reference_initialised_weights_fp32_within_the_fp32_vs_fp64_gap():
+_REFINIT_ORACLE = {}         # (shape) -> the fp32 / fp64 oracle results: one oracle evaluation serves the three modes
+
+
+def _refinit_oracle(sd, shape, img, lab):
+    from oracle import dmlnet_ref as O
+    if shape not in _REFINIT_ORACLE:
+        res = {}
+        for name, dt in (("fp32", torch.float32), ("fp64", torch.float64)):
+            o = O.deeplabv3plus_embedding_resnet101(num_classes=16, output_stride=16)
+            o.load_state_dict(sd)
+            o = o.to(dt)
+            o.train()
+            o.classifier.aspp.project[3].eval()
+            if shape[0] == 1:
+                o.classifier.aspp.convs[4][2].eval()
+            olg, _, _ = o(img.to(dt))
+            ol = O.dml_loss(olg, lab, alpha=0.01, ignore_index=255)
+            ol.backward()
+            res[name] = (olg.detach().double(), float(ol), [p.grad.detach().double().flatten() for p in o.parameters()])
+        _REFINIT_ORACLE.clear()           # (the tests run shape by shape)
+        _REFINIT_ORACLE[shape] = res
+    return _REFINIT_ORACLE[shape]
+
+
+@pytest.mark.parametrize("products", ["exact", "bf16x3", "f16x2"])
+@pytest.mark.parametrize("shape", [(2, 3, 128, 128), (1, 3, 192, 256)], ids=["2x128x128", "1x192x256"])
+def test_reference_initialised_weights_fp32_within_the_fp32_vs_fp64_gap(products, shape):
     """torch.manual_seed(1) + the reference's init (the bench's weights): HIP fp32 step vs the fp64 oracle, bars set by how
-    far the fp32 ORACLE is from the same fp64 evaluation."""
+    far the fp32 ORACLE is from the same fp64 evaluation -- in every fp32 arithmetic mode (exact fp32 MFMA, three-term bf16 split,
+    two fp16 planes: the bench headline), one set of bars.  Batch 1: the image-pooling branch's BatchNorm sees one value per
+    channel, which torch's BatchNorm refuses in training (network/utils.py:318-329 cannot train at batch 1 either), so it runs on
+    its running statistics on both sides; its output is then one constant per channel over the map, which the batch statistics of
+    the ASPP projection's BatchNorm remove, so the gradients of that branch are zero in exact arithmetic and rounding noise in
+    every evaluation (the "max" columns below: ~1e8 relative for the fp32 oracle as for the HIP modes).
+    Measured on the MI355X, HIP vs fp64 (fp32 oracle vs fp64 in brackets) -- logits; gradient max-norm error median / p95:
+      2x3x128x128  exact 6.4e-4; 6.3e-2 / 1.7e-1   bf16x3 8.3e-4; 7.3e-2 / 1.6e-1   f16x2 1.0e-3; 6.5e-2 / 1.7e-1   (7.3e-4; 6.3e-2 / 1.6e-1)
+      1x3x192x256  exact 5.3e-4; 6.5e-2 / 1.8e-1   bf16x3 5.2e-4; 6.6e-2 / 1.8e-1   f16x2 4.5e-4; 5.8e-2 / 1.6e-1   (4.9e-4; 6.2e-2 / 1.7e-1)"""
     import network
     import utils
-    from oracle import dmlnet_ref as O
     torch.set_num_threads(min(64, torch.get_num_threads() or 8))
     torch.manual_seed(1)
     m = network.deeplabv3plus_embedding_resnet101(num_classes=16, output_stride=16, pretrained_backbone=False)
@@ -224,27 +257,20 @@ def test_reference_initialised_weights_fp32_within_the_fp32_vs_fp64_gap():
     assert all(float((g - 1).abs().max()) == 0 for g in gam)          # gamma = 1 everywhere: NOT the conditioned fixture weights
     w = sd["backbone.layer3.5.conv2.weight"]
     assert abs(float(w.std()) - (2.0 / (256 * 9)) ** 0.5) < 0.05 * (2.0 / (256 * 9)) ** 0.5      # kaiming fan_out (resnet.py:156)
-    shape = (2, 3, 128, 128)
-    img = H.synth_tensor(31, "refinit.img", shape)
-    lab = H.synth_labels(31, "refinit.lab", (2, 128, 128), 16, 255, ignore_frac=0.05)
+    B, _, Hh, Ww = shape
+    tag = "" if shape == (2, 3, 128, 128) else ".%dx%dx%d" % (B, Hh, Ww)
+    img = H.synth_tensor(31, "refinit.img" + tag, shape)
+    lab = H.synth_labels(31, "refinit.lab" + tag, (B, Hh, Ww), 16, 255, ignore_frac=0.05)
     m.cuda().train()
-    m.set_compute_dtype(torch.float32)
+    m.set_compute_dtype(torch.float32, fp32_products=products)
     m.classifier.aspp.project[3].eval()
+    if B == 1:
+        m.classifier.aspp.convs[4][2].eval()
     lg, _, ft = m(img.cuda())
     loss = utils.DMLLoss(alpha=0.01, ignore_index=255)(lg, lab.cuda(), ft)
     loss.backward()
     torch.cuda.synchronize()
-    res = {}
-    for name, dt in (("fp32", torch.float32), ("fp64", torch.float64)):
-        o = O.deeplabv3plus_embedding_resnet101(num_classes=16, output_stride=16)
-        o.load_state_dict(sd)
-        o = o.to(dt)
-        o.train()
-        o.classifier.aspp.project[3].eval()
-        olg, _, _ = o(img.to(dt))
-        ol = O.dml_loss(olg, lab, alpha=0.01, ignore_index=255)
-        ol.backward()
-        res[name] = (olg.detach().double(), float(ol), [p.grad.detach().double().flatten() for p in o.parameters()])
+    res = _refinit_oracle(sd, shape, img, lab)
     t_lg, t_loss, t_g = res["fp64"]
     o_lg, o_loss, o_g = res["fp32"]
     h_g = [p.grad.detach().double().cpu().flatten() for p in m.parameters()]
@@ -259,9 +285,9 @@ def test_reference_initialised_weights_fp32_within_the_fp32_vs_fp64_gap():
     eh, ch = gerr(h_g)
     eo, co = gerr(o_g)
     lh, lo_ = H.rel_err(lg, t_lg), H.rel_err(o_lg, t_lg)
-    print("reference-initialised weights, vs fp64 oracle | logits: hip %.2e oracle-fp32 %.2e | loss: hip %.2e oracle-fp32 %.2e | "
+    print("reference-initialised weights, %s %s, vs fp64 oracle | logits: hip %.2e oracle-fp32 %.2e | loss: hip %.2e oracle-fp32 %.2e | "
           "grad max-norm err median/p95/max: hip %.2e %.2e %.2e oracle-fp32 %.2e %.2e %.2e | 1-cos median/max: hip %.2e %.2e "
-          "oracle-fp32 %.2e %.2e" % (lh, lo_, abs(loss.item() - t_loss) / abs(t_loss), abs(o_loss - t_loss) / abs(t_loss),
+          "oracle-fp32 %.2e %.2e" % (products, "x".join(map(str, shape)), lh, lo_, abs(loss.item() - t_loss) / abs(t_loss), abs(o_loss - t_loss) / abs(t_loss),
                                      np.median(eh), np.percentile(eh, 95), eh.max(), np.median(eo), np.percentile(eo, 95), eo.max(),
                                      np.median(ch), ch.max(), np.median(co), co.max()))
     assert torch.isfinite(lg).all()
