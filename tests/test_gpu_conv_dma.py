@@ -26,13 +26,13 @@ def test_every_unit_locally_exact_through_the_256_row_tiles():
     """The 256-row tile of the LDS-DMA kernel (4 waves on 128 x 64 wave tiles, conv_igemm_dma_kernel<.., 256, 128>) runs by itself
     only on the long-K layers (K >= 4608, or the decoder's 3x3 at 16 x 192 x 192); DML_CONV_BM256=2 forces it on every eligible
     layer of a bf16 train step -- fused statistics, fused BN-backward sums, accumulate, the K-split tail -- and every unit must
-    still be exact to one bf16 ulp (all three cases of the locally-exact gate incl. 768 x 768)."""
+    still be exact to one bf16 ulp (all four cases of the locally-exact gate incl. 768 x 768 and the odd 97 x 129)."""
     env = dict(os.environ, DML_CONV_BM256="2")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(H.ROOT, "tests", "test_gpu_bf16_parity.py"), "-m", "gpu",
                         "-q", "-x", "-k", "locally_exact", "-p", "no:cacheprovider"], env=env, capture_output=True, text=True,
                        cwd=H.ROOT, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "3 passed" in r.stdout
+    assert "4 passed" in r.stdout
 
 
 def test_every_unit_locally_exact_through_the_wave_specialised_kernel():
@@ -44,7 +44,7 @@ def test_every_unit_locally_exact_through_the_wave_specialised_kernel():
                         "-q", "-x", "-k", "locally_exact", "-p", "no:cacheprovider"], env=env, capture_output=True, text=True,
                        cwd=H.ROOT, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "3 passed" in r.stdout
+    assert "4 passed" in r.stdout
 
 
 @pytest.mark.parametrize("products", ["exact", "f16x2"])
@@ -226,10 +226,20 @@ def test_train_driver_synthetic_with_raw_label_ids(tmp_path, dtype):
     """main_embedding.py end to end at a small size: raw-id label frames -> crop / jitter / flip / encode_target in one
     kernel -> train steps -> validation (device confusion matrix) -> checkpoint; in the throughput mode and in bench.py's headline
     arithmetic (--dtype f16x2: reachable from the entry point north_star names)."""
+    _train_driver_synthetic(tmp_path, dtype, 128, 160, 224)
+
+
+def test_train_driver_synthetic_odd_crop_f16x2(tmp_path):
+    """The same at an odd crop, 161 (161 -> 81 -> 41 -> 21 -> 11): the drivers' deferred loss gradient is materialised by
+    dml_loss_bwd's scalar kernel (H * W % 4 == 1, upsample 41 -> 161 not x4)."""
+    _train_driver_synthetic(tmp_path, "f16x2", 161, 192, 256)
+
+
+def _train_driver_synthetic(tmp_path, dtype, crop, frame_h, frame_w):
     drv = os.path.join(H.PKG, "main_embedding.py")
-    r = subprocess.run([sys.executable, drv, "--synthetic", "--crop_size", "128", "--batch_size", "4", "--total_itrs", "4",
-                        "--print_interval", "2", "--val_interval", "4", "--val_images", "1", "--frame_height", "160",
-                        "--frame_width", "224", "--loss_type", "dml", "--dtype", dtype, "--save_dir", str(tmp_path)],
+    r = subprocess.run([sys.executable, drv, "--synthetic", "--crop_size", str(crop), "--batch_size", "4", "--total_itrs", "4",
+                        "--print_interval", "2", "--val_interval", "4", "--val_images", "1", "--frame_height", str(frame_h),
+                        "--frame_width", str(frame_w), "--loss_type", "dml", "--dtype", dtype, "--save_dir", str(tmp_path)],
                        capture_output=True, text=True, cwd=H.PKG, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert "Itrs 4/4, Loss=" in r.stdout and "Mean IoU" in r.stdout

@@ -311,10 +311,12 @@ def test_forked_eval_plan_f16x2_is_bitwise_the_unforked_one(monkeypatch):
     assert torch.equal(outs["0"][0], outs["1"][0]) and torch.equal(outs["0"][1], outs["1"][1])
 
 
+@pytest.mark.parametrize("products", ["exact", "bf16x3", "f16x2"])
 @pytest.mark.parametrize("shape", [(1, 3, 65, 97), (3, 3, 50, 34)])
-def test_odd_input_sizes_eval_and_train_forward(shape):
+def test_odd_input_sizes_eval_and_train_forward(shape, products):
     """Sizes that are no multiple of the output stride (ragged tiles everywhere, odd bilinear ratios): eval forward with
-    calibrated running statistics, and the train-mode forward, against the fp64 oracle."""
+    calibrated running statistics, and the train-mode forward, against the fp64 oracle -- in every fp32 arithmetic mode (f16x2: the
+    stem as the direct 7x7 convolution, the eval plan's running-statistics BatchNorm outputs split by dml_h2_split)."""
     from oracle import dmlnet_ref as O
     torch.set_num_threads(min(32, torch.get_num_threads() or 8))
     img = H.synth_tensor(31, "odd.img", shape)
@@ -324,7 +326,7 @@ def test_odd_input_sizes_eval_and_train_forward(shape):
     o.train()
     o.classifier.aspp.project[3].eval()
     if shape[0] > 1:
-        m = build(seed=31)
+        m = build(seed=31, fp32_products=products)
         with torch.no_grad():
             lg, _, ft = m(img.cuda())
             olg, _, oft = o(img.double())
@@ -336,7 +338,7 @@ def test_odd_input_sizes_eval_and_train_forward(shape):
         for _ in range(3):
             o(cal.double())
     o.eval()
-    m = build(train=False, seed=31)
+    m = build(train=False, seed=31, fp32_products=products)
     m.load_state_dict({k: v.float() for k, v in o.state_dict().items()})
     with torch.no_grad():
         lg, _, ft = m(img.cuda())
@@ -372,6 +374,34 @@ def test_against_oracle_nonsquare_strict(products):
     img = H.synth_tensor(11, "g13n.img", (2, 3, 128, 192))
     lab = H.synth_labels(11, "g13n.lab", (2, 128, 192), 16, 255, ignore_frac=0.05)
     _check_against_oracles(m, img, lab, strict=True, seed=11, state=state)
+
+
+@pytest.mark.parametrize("products", ["exact", "bf16x3", "f16x2"])
+def test_against_oracle_offgrid_strict(products):
+    """The train step of an input OFF the output-stride grid, 2 x 3 x 97 x 129 (every map odd: 97 x 129 -> 49 x 65 -> 25 x 33 ->
+    13 x 17 -> 7 x 9), on CONDITIONED weights (tests/tools/mint_golden_nonsquare.py, g13o_offgrid), with the deferred loss gradient the
+    drivers use: the strict bars of the non-square check in every fp32 mode.  H * W is odd (the loss kernels' scalar path) and the
+    final upsample is not x4 (no fused head backward: the deferred gradient is materialised by dml_loss_bwd, then
+    dml_proto_dist_bwd + dml_bilinear_bwd); in f16x2 the stem is the direct 7x7 convolution and no stride-2 data gradient is split
+    into parity classes.  The test asserts that its plan takes those paths before it compares."""
+    from dmlnet import engine as E
+    torch.set_num_threads(min(32, torch.get_num_threads() or 8))
+    shape = (2, 3, 97, 129)
+    assert shape[2] * shape[3] % 4 != 0
+    state = conditioned("g13o_offgrid", 13)
+    m = build(seed=13, fp32_products=products, state=state)
+    img = H.synth_tensor(13, "g13o.img", shape)
+    lab = H.synth_labels(13, "g13o.lab", (2, 97, 129), 16, 255, ignore_frac=0.05)
+
+    def reaches(model):
+        plan = next(p for k, p in model._engine.plans.items() if k[4])
+        assert plan.heads[0].fused_args is None
+        if products == "f16x2":
+            assert not any(isinstance(u.conv, E._S2DConv) for u in plan.units)
+            assert not any(getattr(fn, "__name__", "") == "dml_pack_input_s2d" for fn, _ in plan.fwd)
+            assert not any(getattr(getattr(a, "_obj", None), "sub_grid", 0) for _, args in plan.bwd for a in args)
+
+    _check_against_oracles(m, img, lab, strict=True, seed=13, state=state, fused_backward=True, reaches=reaches)
 
 
 @pytest.mark.parametrize("num_classes,output_stride", [(16, 8), (8, 16), (24, 16), (32, 8), (21, 16), (13, 16)])
@@ -418,14 +448,19 @@ def test_default_factory_arguments_bf16_features_have_num_classes_channels():
     assert g.shape == (21, 256, 1, 1) and torch.isfinite(g).all() and g.abs().max() > 0
 
 
-def _check_against_oracles(m, img, lab, strict, seed=9, num_classes=16, output_stride=16, prep=None, state=None):
+def _check_against_oracles(m, img, lab, strict, seed=9, num_classes=16, output_stride=16, prep=None, state=None, fused_backward=False,
+                           reaches=None):
+    """fused_backward: the loss hands the model a deferred gradient (as the drivers build it); reaches(m): assertions on the model
+    after its step, before anything is compared"""
     import utils
     from oracle import dmlnet_ref as O
     if prep is not None:
         prep(m)
     lg, _, ft = m(img.cuda())
-    loss = utils.DMLLoss(alpha=0.01, ignore_index=255)(lg, lab.cuda(), ft)
+    loss = utils.DMLLoss(alpha=0.01, ignore_index=255, fused_backward=fused_backward)(lg, lab.cuda(), ft)
     loss.backward()
+    if reaches is not None:
+        reaches(m)
     ref = {}
     for name, dt in (("f32", torch.float32), ("f64", torch.float64)):
         o = O.deeplabv3plus_embedding_resnet101(num_classes=num_classes, output_stride=output_stride)

@@ -66,6 +66,8 @@ CONV_CASES = [
     ("3x3_d6", 2, 8, 8, 128, 256, 3, 1, 6),
     ("3x3_c320", 1, 9, 9, 320, 256, 3, 1, 1),
     ("7x7_s2_stem", 2, 22, 18, 8, 64, 7, 2, 1),
+    # an odd image (crop 513 and the like): the stem cannot take the space-to-depth form, every plan runs the direct 7x7 stride 2
+    ("7x7_s2_stem_odd", 2, 33, 27, 8, 64, 7, 2, 1),
     ("1x1_pool_rows", 4, 1, 1, 256, 256, 1, 1, 1),
 ]
 
@@ -121,7 +123,7 @@ def test_conv_fwd_dgrad_wgrad(lib, case, dname):
         relclose(rv.cpu(), (0.9 + 0.1 * yr.var(dim=(0, 2, 3), unbiased=True)).float(), stol, "running_var " + name)
 
     # data gradient (transposed conv as a gather)
-    if name != "7x7_s2_stem":
+    if not name.startswith("7x7_s2_stem"):
         gyd = nhwc(gy, tdt)
         dxd = torch.full((B, Hh, Ww, Cin), 7.0, device="cuda", dtype=tdt)
         dd = make_desc(lib, gyd, wtd, dxd, B, Ho, Wo, Cout, Hh, Ww, Cin, k, stride, dil, pad, dt, mode=1)
@@ -1300,7 +1302,12 @@ def test_dgrad_rounds_a_staged_gradient_once(lib, shape):
     assert lib.dml_conv_igemm(C.byref(d), st()) != 0
 
 
-@pytest.mark.parametrize("case", [c for c in CONV_CASES if c[4] % 32 == 0], ids=[c[0] for c in CONV_CASES if c[4] % 32 == 0])
+# the bf16x3 and f16x2 plans run an odd image's stem (8 padded channels) with f32_split set: the forward falls back to the exact kernel
+# (C % 32), the weight gradient is the split kernel's (three-term, or both operands as fp16 planes)
+X3_CASES = [c for c in CONV_CASES if c[4] % 32 == 0 or c[0] == "7x7_s2_stem_odd"]
+
+
+@pytest.mark.parametrize("case", X3_CASES, ids=[c[0] for c in X3_CASES])
 def test_conv_f32_three_term_split_is_fp32_accurate(lib, case):
     """DmlConvDesc.f32_split: fp32 tensors, products on the bf16 matrix cores through hi + mid + lo of both operands (six bf16
     MFMAs per block).  Forward (with BN statistics) and data gradient against an fp64 torch convolution: the error must be at
@@ -1328,10 +1335,12 @@ def test_conv_f32_three_term_split_is_fp32_accurate(lib, case):
         dxd = torch.empty((B, Hh, Ww, Cin), device="cuda")
         dd = make_desc(lib, gyd, wtd, dxd, B, Ho, Wo, Cout, Hh, Ww, Cin, k, stride, dil, pad, 0, mode=1)
         dd.f32_split = split
-        chk(lib.dml_conv_igemm(C.byref(dd), st()))
+        stem = name.startswith("7x7_s2_stem")                 # (no plan computes the stem's data gradient)
+        if not stem:
+            chk(lib.dml_conv_igemm(C.byref(dd), st()))
         torch.cuda.synchronize()
         ef = (nchw(yd).double() - y_ref.detach()).abs().max().item() / y_ref.detach().abs().max().item()
-        eg = (nchw(dxd).double() - x.grad).abs().max().item() / x.grad.abs().max().item()
+        eg = 0.0 if stem else (nchw(dxd).double() - x.grad).abs().max().item() / x.grad.abs().max().item()
         # statistics partials: sum over each 64-row group of the fp32 accumulators
         yflat = y_ref.detach().permute(0, 2, 3, 1).reshape(M, Cout)
         g0 = yflat[:min(64, M)].sum(0)
@@ -1477,7 +1486,10 @@ H2_CASES = [("h2_1x1", 2, 24, 20, 64, 128, 1, 1, 1), ("h2_3x3", 2, 19, 23, 64, 2
             # dilated 3x3 on a 48 x 48 map (the ASPP branches): whole filter rows are padding for the tiles at the top and the bottom of an
             # image and their K steps are skipped (ws_live_taps) -- 144-row tiles forward and data gradient, 192-row tiles (64 channels)
             ("h2_3x3_d12_48", 2, 48, 48, 256, 256, 3, 1, 12), ("h2_3x3_d18_48", 1, 48, 48, 64, 256, 3, 1, 18),
-            ("h2_3x3_d6_40x48", 2, 40, 48, 128, 128, 3, 1, 6)]
+            ("h2_3x3_d6_40x48", 2, 40, 48, 128, 128, 3, 1, 6),
+            # the stem of an odd image in the f16x2 plan: forward and data gradient are no shapes of the planes kernel, the weight
+            # gradient reads both operands as planes (8 channels, 7 x 7 taps, stride 2)
+            ("h2_7x7_s2_stem_odd", 2, 33, 27, 8, 64, 7, 2, 1)]
 
 
 @pytest.mark.parametrize("case", H2_CASES, ids=lambda c: c[0])
@@ -1505,11 +1517,13 @@ def test_conv_f16_two_plane_split_is_fp32_accurate(lib, case):
         dxd = torch.empty((B, Hh, Ww, Cin), device="cuda")
         dd = make_desc(lib, gyd, wtd, dxd, B, Ho, Wo, Cout, Hh, Ww, Cin, k, stride, dil, pad, 0, mode=1)
         keep = []
+        fwd_planes = False
         if split:
             for desc, act, wmat, rows_w in ((d, xd, wd, Cout), (dd, gyd, wtd, Cin)):
-                if rows_w % 64:                      # not a shape of the planes kernel: the three-term split takes it
+                if rows_w % 64 or (wmat.numel() // rows_w) % 32:     # not a shape of the planes kernel: the three-term split takes it
                     desc.f32_split = 1
                     continue
+                fwd_planes = fwd_planes or desc is d
                 ap, aw = h2_planes(lib, act.view(-1, act.shape[-1]), 0)
                 wp, ww = h2_planes(lib, wmat.view(rows_w, -1), 1)
                 keep += [ap, aw, wp, ww]
@@ -1520,18 +1534,20 @@ def test_conv_f16_two_plane_split_is_fp32_accurate(lib, case):
         # two-plane forward: one partial per 144-row wave tile -- 48 rows on the 48-row wave tiles (64 output channels; 48 x 256 tiles of
         # launches with at most 128 tiles of 144 x 256)
         short = Cout % 256 == 0 and ((M + 143) // 144) * (Cout // 256) * 2 <= 256
-        assert rows == ((48 if (Cout == 64 or short) else 144) if (split and Cout % 64 == 0) else 64)
+        assert rows == ((48 if (Cout == 64 or short) else 144) if fwd_planes else 64)
         stats = torch.zeros((M + rows - 1) // rows * Cout * 2, device="cuda")
         d.stats = stats.data_ptr()
         chk(lib.dml_conv_igemm(C.byref(d), st()))
-        chk(lib.dml_conv_igemm(C.byref(dd), st()))
+        stem = name.startswith("h2_7x7_s2_stem")              # (no plan computes the stem's data gradient)
+        if not stem:
+            chk(lib.dml_conv_igemm(C.byref(dd), st()))
         sc, sh, mu, inv = (torch.empty(Cout, device="cuda") for _ in range(4))
         chk(lib.dml_bn_finalize(stats.data_ptr(), M, Cout, rows, None, None, None, None, 0.1, 1e-5, sc.data_ptr(), sh.data_ptr(),
                                 mu.data_ptr(), inv.data_ptr(), st()))
         torch.cuda.synchronize()
         yr = y_ref.detach()
         ef = (nchw(yd).double() - yr).abs().max().item() / yr.abs().max().item()
-        eg = (nchw(dxd).double() - x.grad).abs().max().item() / x.grad.abs().max().item()
+        eg = 0.0 if stem else (nchw(dxd).double() - x.grad).abs().max().item() / x.grad.abs().max().item()
         em = (mu.cpu().double() - yr.mean(dim=(0, 2, 3))).abs().max().item() / yr.abs().max().item()
         # weight gradient (workspace path): both operands as planes
         from dmlnet._lib import WgradDesc
@@ -1884,3 +1900,215 @@ def test_tile_major_weights_are_bit_identical(lib, case):
     assert lib.dml_conv_igemm(C.byref(bad), st()) != 0
     d.N = Cout - 16
     assert lib.dml_conv_igemm(C.byref(d), st()) != 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Odd crop sizes (crop 513: 513 -> 257 -> 129 -> 65 -> 33): the loss kernels' scalar path, the head at upsampling ratios other than
+# x4, the decoder's fractional resize -- each against a float64 evaluation of the same operation
+# ---------------------------------------------------------------------------------------------------------------------------------
+LOSS_CASES = [
+    # name, B, K, H, W, ignore_index, which pixels are ignored
+    ("hw1_65x97", 2, 16, 65, 97, 255, "5%"),              # H * W % 4 == 1: loss_fwd_kernel<1> / loss_bwd_kernel<1>
+    ("hw3_31x33_k32", 2, 32, 31, 33, 255, "5%"),          # % 4 == 3, the widest K
+    ("hw0_50x34_k13", 3, 13, 50, 34, -1, "5%"),           # % 4 == 0: the vector kernels (control)
+    ("hw3_7x9_image1_ignored", 2, 21, 7, 9, 255, "image1"),   # an image without a valid pixel still counts in n
+    ("hw1_513_grid_stride", 4, 16, 513, 513, 255, "5%"),  # 1.05 M pixels: the grid-stride loop over the 2048-block cap
+]
+
+
+def _loss_logits(name, B, K, Hh, Ww, regime):
+    """negative squared distances: 'spread' of order 10 .. 300; 'close' of order 1e4 with the top two classes less than 1 apart"""
+    if regime == "spread":
+        return -(10.0 + 290.0 * H.synth_tensor(41, name + ".u", (B, K, Hh, Ww), kind="uniform").abs())
+    lg = -(1e4 + 300.0 * H.synth_tensor(41, name + ".u", (B, K, Hh, Ww), kind="uniform").abs())
+    top = lg.max(1).values
+    k2 = torch.from_numpy(H.rng_for(41, name + ".k2").integers(0, K, size=(B, Hh, Ww)))
+    gap = H.synth_tensor(41, name + ".gap", (B, Hh, Ww), kind="uniform").abs() * 0.99
+    lg.scatter_(1, k2.unsqueeze(1), (top - gap).unsqueeze(1))          # a runner-up within 1 of the top (or a new top)
+    return lg
+
+
+@pytest.mark.parametrize("regime", ["spread", "close"])
+@pytest.mark.parametrize("alpha", [0.01, 0.0])
+@pytest.mark.parametrize("case", LOSS_CASES, ids=[c[0] for c in LOSS_CASES])
+def test_dml_loss_against_fp64(lib, case, alpha, regime):
+    """dml_loss_fwd -> dml_loss_finalize -> dml_loss_bwd (utils.DMLLoss, materialised gradient, gout = 0.5) against the oracle's
+    DML loss in float64 autograd; then the same sums through the data-parallel branch of the C ABI (n_images = 0: the image count
+    read from sums[4] on the device).  G2's bars: loss 1e-5 relative, gradient 1e-5 of its max magnitude."""
+    import utils
+    from dmlnet import _lib as L
+    from oracle import dmlnet_ref as O
+    name, B, K, Hh, Ww, ign, which = case
+    lg = _loss_logits(name, B, K, Hh, Ww, regime)
+    if which == "image1":
+        lab = H.synth_labels(41, name + ".lab", (B, Hh, Ww), K, ign)
+        lab[1] = ign
+    else:
+        lab = H.synth_labels(41, name + ".lab", (B, Hh, Ww), K, ign, ignore_frac=0.05)
+    lo64 = lg.double().requires_grad_(True)
+    ref = O.dml_loss(lo64, lab, alpha=alpha, ignore_index=ign)
+    (ref * 0.5).backward()
+    ref_loss, ref_grad = ref.item(), lo64.grad
+    gscale = ref_grad.abs().max().item()
+
+    lo = lg.cuda().requires_grad_(True)
+    lab_d = lab.cuda()
+    loss = utils.DMLLoss(alpha=alpha, ignore_index=ign, fused_backward=False)(lo, lab_d)
+    (loss * 0.5).backward()
+    torch.cuda.synchronize()
+    el = abs(loss.item() - ref_loss) / abs(ref_loss)
+    eg = (lo.grad.cpu().double() - ref_grad).abs().max().item() / gscale
+    # the same through the C ABI with the image count on the device (parallel.py's all-reduced sums)
+    sums = torch.zeros(5, dtype=torch.float64, device="cuda")
+    part = torch.empty(L.LOSS_BLOCKS * 4, dtype=torch.float32, device="cuda")
+    lgd = lo.detach()
+    chk(lib.dml_loss_fwd(lgd.data_ptr(), lab_d.data_ptr(), sums.data_ptr(), part.data_ptr(), B, K, Hh, Ww, ign, st()))
+    sums[4] = float(B)
+    loss2 = torch.empty((), device="cuda")
+    chk(lib.dml_loss_finalize(sums.data_ptr(), loss2.data_ptr(), alpha, 0.0, st()))
+    gout = torch.tensor(0.5, device="cuda")
+    g2 = torch.full_like(lgd, float("nan"))
+    chk(lib.dml_loss_bwd(lgd.data_ptr(), lab_d.data_ptr(), sums.data_ptr(), gout.data_ptr(), g2.data_ptr(), B, K, Hh, Ww, ign, alpha,
+                         0.0, st()))
+    torch.cuda.synchronize()
+    el2 = abs(loss2.item() - ref_loss) / abs(ref_loss)
+    eg2 = (g2.cpu().double() - ref_grad).abs().max().item() / gscale
+    print("%s alpha %g %s: loss rel err %.2e (n on device %.2e), grad err / max %.2e (%.2e)" % (name, alpha, regime, el, el2, eg, eg2))
+    assert el <= 1e-5 and el2 <= 1e-5
+    assert eg <= 1e-5 and eg2 <= 1e-5
+
+
+@pytest.mark.parametrize("B,Hh,Ww", [(2, 5, 7), (2, 6, 10)], ids=["hw3", "hw0"])
+def test_dml_loss_with_every_pixel_ignored(lib, B, Hh, Ww):
+    """No valid pixel in the batch: the loss is NaN (mean over nothing, as torch's) and the gradient exactly zero -- what torch's
+    autograd gives for the same loss -- in the scalar and in the vector kernel."""
+    import utils
+    from oracle import dmlnet_ref as O
+    lg = _loss_logits("allign%d" % (Hh * Ww), B, 16, Hh, Ww, "spread")
+    lab = torch.full((B, Hh, Ww), 255, dtype=torch.int64)
+    lo64 = lg.double().requires_grad_(True)
+    ref = O.dml_loss(lo64, lab, alpha=0.01, ignore_index=255)
+    (ref * 0.5).backward()
+    assert np.isnan(ref.item()) and torch.equal(lo64.grad, torch.zeros_like(lo64.grad))
+    lo = lg.cuda().requires_grad_(True)
+    loss = utils.DMLLoss(alpha=0.01, ignore_index=255, fused_backward=False)(lo, lab.cuda())
+    (loss * 0.5).backward()
+    torch.cuda.synchronize()
+    assert np.isnan(loss.item())
+    assert torch.equal(lo.grad.cpu(), torch.zeros_like(lg))
+
+
+def _dist_logits64(feats, protos):
+    """-|f - m_k|^2 over the last axis of feats [B,H,W,C] (fp64), expanded: no B x H x W x K x C intermediate at 513 x 513"""
+    f2 = (feats * feats).sum(-1, keepdim=True)
+    return -(f2 - 2.0 * feats @ protos.t() + (protos * protos).sum(-1)).permute(0, 3, 1, 2)
+
+
+HEAD_GEOMS = [(2, 17, 25, 65, 97), (2, 33, 33, 129, 129), (1, 129, 129, 513, 513)]      # B, h, w, H, W of crops 257, 513 and 2049
+
+
+@pytest.mark.parametrize("dname", ["f32", "bf16"])
+@pytest.mark.parametrize("K,Kp", [(16, 16), (13, 16), (21, 24)])
+@pytest.mark.parametrize("geom", HEAD_GEOMS, ids=["%dx%d_to_%dx%d" % g[1:] for g in HEAD_GEOMS])
+def test_head_at_upsampling_ratios_other_than_x4(lib, geom, K, Kp, dname):
+    """The head of an odd crop: dml_upsample_dist_fwd (bilinear resize by a ratio that is not an integer + distance head) and the
+    unfused backward the plan runs there (dml_proto_dist_bwd + dml_bilinear_bwd, fp32 gradient in, `dtype` out), with the embedding
+    carried zero-padded to Kp channels and the prototypes [K][Kp] as the plan holds them, against fp64 autograd of
+    F.interpolate(align_corners=False) + the distance head.  The file's fp32 bar holds against fp64 here too: the kernels' source
+    coordinates are fp32 (as F.interpolate's on fp32 tensors), one ulp of a coordinate near 128 moves a weight by 1.5e-5."""
+    dt, tdt, tol = DT[dname]
+    B, h, w, Hh, Ww = geom
+    tag = "%d_%d_%d" % (h, Hh, K)
+    emb = torch.zeros(B, Kp, h, w, dtype=torch.float64)
+    emb[:, :K] = rnd("hx.e" + tag, (B, K, h, w), 1.5).double()
+    emb.requires_grad_(True)
+    protos = torch.zeros(K, Kp, dtype=torch.float64)
+    protos[:, :K] = 3.0 * torch.eye(K) + 0.05 * rnd("hx.p" + tag, (K, K)).double()
+    up = F.interpolate(emb, size=(Hh, Ww), mode="bilinear", align_corners=False)
+    feats = up.permute(0, 2, 3, 1)
+    logits = _dist_logits64(feats, protos)
+    gl = rnd("hx.gl" + tag, (B, K, Hh, Ww))
+    gf = rnd("hx.gf" + tag, (B, Hh, Ww, Kp)) if dname == "f32" else None      # (the plan passes no feature gradient)
+    obj = (logits * gl.double()).sum()
+    if gf is not None:
+        obj = obj + (feats * gf.double()).sum()
+    obj.backward()
+
+    ed = emb.detach().float().permute(0, 2, 3, 1).contiguous().cuda()
+    pr = protos.float().cuda()
+    lg = torch.empty((B, K, Hh, Ww), device="cuda")
+    ft = torch.empty((B, Hh, Ww, Kp), device="cuda")
+    chk(lib.dml_upsample_dist_fwd(ed.data_ptr(), pr.data_ptr(), lg.data_ptr(), ft.data_ptr(), None, None, B, h, w, Kp, K, Hh, Ww,
+                                  st()))
+    df = torch.empty((B, Hh, Ww, Kp), device="cuda")
+    gld = gl.cuda()
+    gfd = gf.cuda() if gf is not None else None
+    chk(lib.dml_proto_dist_bwd(gld.data_ptr(), gfd.data_ptr() if gfd is not None else None, ft.data_ptr(), pr.data_ptr(),
+                               df.data_ptr(), B, Kp, K, Hh, Ww, st()))
+    de = torch.empty((B, h, w, Kp), device="cuda", dtype=tdt)
+    chk(lib.dml_bilinear_bwd(df.data_ptr(), de.data_ptr(), B, h, w, Hh, Ww, Kp, Kp, Kp, dt, 1, 0, st()))
+    torch.cuda.synchronize()
+    e_lg = (lg.cpu().double() - logits.detach()).abs().max().item() / logits.detach().abs().max().item()
+    e_ft = (ft.cpu().double() - feats.detach()).abs().max().item() / feats.detach().abs().max().item()
+    gref = emb.grad.permute(0, 2, 3, 1)
+    e_de = (de.float().cpu().double() - gref).abs().max().item() / gref.abs().max().item()
+    print("%s K %d/%d %s: logits %.2e features %.2e embedding gradient %.2e" % (tag, K, Kp, dname, e_lg, e_ft, e_de))
+    assert e_lg <= DT["f32"][2] and e_ft <= DT["f32"][2]
+    assert e_de <= tol
+
+
+@pytest.mark.parametrize("dname", ["f32", "bf16"])
+@pytest.mark.parametrize("geom", [(2, 7, 9, 25, 33), (2, 33, 33, 129, 129)], ids=["7x9_to_25x33", "33x33_to_129x129"])
+def test_decoder_resize_into_a_channel_slice(lib, geom, dname):
+    """The decoder's resize of the ASPP projection (256 channels) into channels 48 .. 303 of the concat buffer, and its transpose
+    reading that slice back, as the plan does it (the concat rows are 320 wide; 304, the unpadded width, as well), at fractional
+    ratios: against fp64 F.interpolate and its autograd; the buffer's other channels stay untouched."""
+    dt, tdt, tol = DT[dname]
+    B, h, w, Hh, Ww = geom
+    Cc = 256
+    x = qz(rnd("dr.x%d" % h, (B, Cc, h, w)), tdt).double().requires_grad_(True)
+    y = F.interpolate(x, size=(Hh, Ww), mode="bilinear", align_corners=False)
+    gy = qz(rnd("dr.g%d" % h, tuple(y.shape)), tdt).double()
+    y.backward(gy)
+    xd = nhwc(x.detach().float(), tdt)
+    for ld in (320, 304):
+        buf = torch.full((B, Hh, Ww, ld), 7.0, device="cuda", dtype=tdt)
+        chk(lib.dml_bilinear_fwd(xd.data_ptr(), buf[..., 48:].data_ptr(), B, h, w, Hh, Ww, Cc, Cc, ld, dt, 0, 0, st()))
+        dcat = torch.full((B, Hh, Ww, ld), float("nan"), device="cuda", dtype=tdt)
+        dcat[..., 48:48 + Cc] = nhwc(gy.float(), tdt)
+        dx = torch.empty((B, h, w, Cc), device="cuda", dtype=tdt)
+        chk(lib.dml_bilinear_bwd(dcat[..., 48:].data_ptr(), dx.data_ptr(), B, h, w, Hh, Ww, Cc, ld, Cc, dt, 0, 0, st()))
+        torch.cuda.synchronize()
+        assert (buf[..., :48] == 7.0).all() and (buf[..., 48 + Cc:] == 7.0).all()
+        ef = (nchw(buf[..., 48:48 + Cc]).double() - y.detach()).abs().max().item() / y.detach().abs().max().item()
+        eb = (nchw(dx).double() - x.grad).abs().max().item() / x.grad.abs().max().item()
+        print("ld %d %s: resize %.2e transpose %.2e" % (ld, dname, ef, eb))
+        assert ef <= max(tol, 1e-6) and eb <= max(tol, 1e-5)
+
+
+@pytest.mark.parametrize("bound", [1.0, 5.3])
+@pytest.mark.parametrize("geom", [(2, 7, 9, 25, 33), (2, 33, 33, 129, 129)], ids=["7x9_to_25x33", "33x33_to_129x129"])
+def test_bilinear_fwd_planes_equals_resize_then_split(lib, geom, bound):
+    """dml_bilinear_fwd_planes (the f16x2 training plan's decoder concat buffer, which exists as fp16 planes only) against
+    dml_bilinear_fwd into the fp32 slice followed by dml_h2_split with the same scale: the header promises dml_h2_split's
+    arithmetic on the value dml_bilinear_fwd would store, so hi and lo must be BIT-EQUAL.  The scale comes from a bound on the
+    maximum (the plan's comes from the BatchNorms' bounds): exactly max |x| (bound 1) and a few binades above it."""
+    B, h, w, Hh, Ww = geom
+    Cc, ld = 256, 320
+    x = nhwc(rnd("bp.x%d" % h, (B, Cc, h, w)), torch.float32)
+    cat = torch.zeros((B, Hh, Ww, ld), device="cuda")
+    chk(lib.dml_bilinear_fwd(x.data_ptr(), cat[..., 48:].data_ptr(), B, h, w, Hh, Ww, Cc, Cc, ld, 0, 0, 0, st()))
+    rows = B * Hh * Ww
+    ref = torch.zeros((2, rows * ld), device="cuda", dtype=torch.float16)
+    work = torch.zeros(1025, device="cuda")
+    work[3] = x.abs().max() * bound
+    chk(lib.dml_h2_split(cat[..., 48:].data_ptr(), rows, Cc, ld, ref[:, 48:].data_ptr(), rows * ld, ld, 0, work.data_ptr(), 1, st()))
+    got = torch.full((2, rows * ld), 3.0, device="cuda", dtype=torch.float16)
+    chk(lib.dml_bilinear_fwd_planes(x.data_ptr(), got[:, 48:].data_ptr(), rows * ld, ld, work[1024:].data_ptr(), B, h, w, Hh, Ww, Cc,
+                                    Cc, st()))
+    torch.cuda.synchronize()
+    got, ref = got.view(2, rows, ld), ref.view(2, rows, ld)
+    assert (got[:, :, :48] == 3.0).all() and (got[:, :, 48 + Cc:] == 3.0).all()
+    for p_, what in ((0, "hi"), (1, "lo")):
+        diff = (got[p_, :, 48:48 + Cc] != ref[p_, :, 48:48 + Cc]).sum().item()
+        assert diff == 0, "%s plane: %d of %d elements differ" % (what, diff, rows * Cc)

@@ -176,6 +176,22 @@ def test_nonsquare_conditioning_record_g13n():
     m.load_state_dict(sd)
 
 
+def test_offgrid_conditioning_record_g13o():
+    """tests/golden/g13o_offgrid.npz (tests/tools/mint_golden_nonsquare.py): the moved BatchNorm betas of the off-grid 2 x 3 x 97 x 129
+    live-oracle check (every map odd) and the proof numbers the mint script asserted on the reference."""
+    g = H.load_golden("g13o_offgrid")
+    assert int(g["seed"]) == 13 and tuple(int(v) for v in g["shape"]) == (2, 3, 97, 129)
+    assert float(g["relu_margin"]) >= 64.0 and float(g["relu_margin_over_noise"]) >= 6.0 and int(g["relu_elems"]) > 10_000_000
+    assert (g["relu_margins"] >= np.maximum(64.0, 6.0 * g["relu_fp32_noise"])).all() and int(g["beta_moved"]) == g["beta_idx"].size
+    m = O.deeplabv3plus_embedding_resnet101(num_classes=16, output_stride=16)
+    sd = H.conditioned_state_dict(H.shapes_of(m), 13, g["beta_idx"], g["beta_val"])
+    plain = H.synth_state_dict(H.shapes_of(m), seed=13)
+    moved = [k for k in sd if not torch.equal(sd[k], plain[k])]
+    assert moved and all(k.endswith(".bias") and k[:-4] + "running_mean" in sd for k in moved)       # only BatchNorm betas
+    assert max(float((sd[k] - plain[k]).abs().max()) for k in moved) <= float(g["beta_max_delta"]) + 1e-12
+    m.load_state_dict(sd)
+
+
 @pytest.mark.parametrize("os_", [8, 16])
 def test_variant_conditioning_records_g14v(os_):
     """tests/golden/g14v_os<OS>.npz (tests/tools/mint_golden_variants.py): moved BatchNorm betas of the factory-variant checks and the
