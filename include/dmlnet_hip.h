@@ -546,6 +546,35 @@ int dml_label_encode(const uint8_t* raw, int64_t n, const uint8_t* lut, const ui
                      int64_t* out, int64_t* out_true, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation input of the anomaly sub-project (anomaly/dataset.py:249-300 of the reference, ValDataset):
+ * one decoded uint8 HWC RGB frame -> every scale of the multi-scale test, each equal bit for bit to
+ * img_transform(imresize(img, (W_s, H_s), 'bilinear')).  The resampler is Pillow's 8-bit one
+ * (libImaging/Resample.c): per-axis coefficients rounded to fixed point with 22 fraction bits (built on
+ * the host in double), a horizontal pass over the source rows the vertical pass reads, rounded to uint8
+ * (int32 accumulator from 2^21, (acc >> 22) clamped to [0,255]), then a vertical pass over that uint8
+ * intermediate rounded the same way.  Normalisation in fp32 with true divisions: (v/255 - mean_c)/std_c.
+ * ---------------------------------------------------------------------------------------------- */
+#define DML_RESIZE_MAX_SCALES 8
+typedef struct DmlResizeScale {
+    float* out;                 /* [3, Hs, Ws] fp32 (the [1, 3, Hs, Ws] NCHW tensor of one scale)             */
+    const int32_t* hbounds;     /* [Ws][2] (first source column, tap count) of each output column (device)     */
+    const int32_t* hcoef;       /* [Ws][kh] fixed-point weights of those columns (device)                      */
+    const int32_t* vbounds;     /* [Hs][2] (first source row, tap count) of each output row (device)           */
+    const int32_t* vcoef;       /* [Hs][kv] (device)                                                          */
+    int32_t Hs, Ws, kh, kv;
+    int32_t band_rows;          /* output rows of one workgroup (a band of 64 columns)                         */
+    int32_t lds_rows;           /* upper bound of the source rows any band of this scale reads (<= 256)        */
+} DmlResizeScale;
+/* All S (1..DML_RESIZE_MAX_SCALES) scales of frame img[h][w][3] (device uint8) in one launch.  `scales`
+ * is a HOST array read during the call (its pointers are device pointers); the tables must have been
+ * built for this (h, w).  DML_EUNSUPPORTED when a band needs more than 256 source rows. */
+int dml_pil_resize_normalize(const uint8_t* img, int h, int w, const DmlResizeScale* scales, int S,
+                             float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                             void* stream);
+/* segm_transform of the same dataset: out[i] = (int64) segm[i] - 1 (an 'L' annotation; 0 becomes -1). */
+int dml_segm_to_label(const uint8_t* segm, int64_t n, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pyramid-pooling decoder of the anomaly model (anomaly/models/models.py:586-687,
  * eval_ood_traditional.py:198-210 of the reference), inference only.
  * ---------------------------------------------------------------------------------------------- */

@@ -98,6 +98,15 @@ class AugSample(C.Structure):
                 ("op", C.c_int32 * 3), ("factor", C.c_float * 3)]
 
 
+class ResizeScale(C.Structure):
+    """DmlResizeScale: one target size of a dml_pil_resize_normalize launch"""
+    _fields_ = [("out", c_p), ("hbounds", c_p), ("hcoef", c_p), ("vbounds", c_p), ("vcoef", c_p),
+                ("Hs", C.c_int32), ("Ws", C.c_int32), ("kh", C.c_int32), ("kv", C.c_int32),
+                ("band_rows", C.c_int32), ("lds_rows", C.c_int32)]
+
+
+RESIZE_MAX_SCALES = 8
+
 _PROTOS = {
     "dml_abi_version": (c_i, []),
     "dml_target_arch": (C.c_char_p, []),
@@ -171,6 +180,8 @@ _PROTOS = {
     "dml_aug_apply_encoded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f,
                                     c_p, c_p, c_p, c_p]),
     "dml_label_encode": (c_i, [c_p, C.c_int64, c_p, c_p, c_p, c_p, c_p]),
+    "dml_pil_resize_normalize": (c_i, [c_p, c_i, c_i, C.POINTER(ResizeScale), c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
+    "dml_segm_to_label": (c_i, [c_p, c_i64, c_p, c_p]),
     "dml_adaptive_avgpool_ws_elems": (c_i64, [c_i, c_i, c_i, c_i, c_i]),
     "dml_adaptive_avgpool_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_proto_dist_nhwc": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),

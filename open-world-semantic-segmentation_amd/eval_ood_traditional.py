@@ -7,9 +7,13 @@ upsample kernel, scales concurrent), `pred = argmax` (:218), the confidence map 
 (:275-340: msp | maxlogit | dissum | background; the CRF / kNN variants of the reference need pydensecrf / are
 plotting experiments and are not offered), then `eval_ood_measure` (:128-148) and the pixel accuracy / IoU meters
 (:548-556) -- all on the device; nothing but the three OOD numbers and the confusion counts per frame reaches the host.
-Data: `--synthetic` frames only (decoding / PIL-resizing StreetHazards PNGs is dataset IO, outside the build's scope).
+Data: a StreetHazards-layout tree from disk (the reference's command line: `--cfg FILE`, `--gpu`, `--ood`,
+`--exclude_back` and trailing `KEY VALUE` overrides; datasets/streethazards.py decodes on host threads and resizes /
+normalises on the device, bit for bit the reference's ValDataset tensors), or `--synthetic` frames.
 """
 import argparse
+import ast
+import os
 import time
 
 import numpy as np
@@ -26,13 +30,8 @@ IMG_SIZES, IMG_MAX_SIZE, PADDING_CONSTANT = (300, 375, 450, 525, 600), 1000, 8
 def resized_shapes(h, w):
     """dataset.py's TestDataset sizes: short side -> each of IMG_SIZES, long side <= IMG_MAX_SIZE, both rounded up to a
     multiple of PADDING_CONSTANT."""
-    out = []
-    for short in IMG_SIZES:
-        sc = min(short / float(min(h, w)), IMG_MAX_SIZE / float(max(h, w)))
-        th, tw = int(h * sc), int(w * sc)
-        out.append(((th + PADDING_CONSTANT - 1) // PADDING_CONSTANT * PADDING_CONSTANT,
-                    (tw + PADDING_CONSTANT - 1) // PADDING_CONSTANT * PADDING_CONSTANT))
-    return out
+    from datasets.streethazards import resized_shapes as shapes
+    return shapes(h, w, IMG_SIZES, IMG_MAX_SIZE, PADDING_CONSTANT)
 
 
 def confidence(scores, ood, exclude_back=False):
@@ -54,11 +53,13 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
     """frames: iterable of (img_resized_list, seg_label int64 [H, W]) on the device."""
     seg_metrics = metrics_mod.StreamSegMetrics(num_class)
     aurocs, auprs, fprs, times = [], [], [], []
+    known = num_class
     for imgs, seg_label in frames:
         torch.cuda.synchronize()
         tic = time.perf_counter()
         seg_size = tuple(seg_label.shape)
         scores, ft1 = models.evaluate_multiscale(segmentation_module, imgs, seg_size)
+        known = scores.shape[1]
         pred = utils.argmax_msp(scores)[0]
         conf = confidence(scores, ood, exclude_back)
         res = anom_utils.eval_ood_measure(conf, seg_label, out_labels)
@@ -70,7 +71,65 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
     return {"auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
             "aupr": float(np.mean(auprs)) if auprs else float("nan"),
             "fpr": float(np.mean(fprs)) if fprs else float("nan"),
-            "seg": seg_metrics.get_results(), "sec_per_frame": float(np.mean(times[1:] or times))}
+            "seg": seg_metrics.get_results(), "sec_per_frame": float(np.mean(times[1:] or times)),
+            "known_iou": known_class_iou(seg_metrics, known)}
+
+
+def known_class_iou(seg_metrics, known):
+    """The reference's per-class IoU (utils.py intersectionAndUnion(pred, label, num_class) summed over frames, then
+    intersection / (union + 1e-10)): the first `known` classes of the confusion matrix only -- the model's classes,
+    not the anomaly label -- and a class that never occurs counts as 0.  Its mean is the reference's `Mean IoU`."""
+    if seg_metrics.confusion_matrix is None:
+        return np.zeros(known)
+    counts = seg_metrics.confusion_matrix.cpu().numpy().astype(np.float64)
+    tp = np.diag(counts)[:known]
+    union = counts.sum(axis=1)[:known] + counts.sum(axis=0)[:known] - tp
+    return tp / (union + 1e-10)
+
+
+# the configuration keys the real-data run honours (anomaly/config/defaults.py of the reference for the defaults)
+CFG_DEFAULTS = {
+    "DATASET.root_dataset": "./data/",
+    "DATASET.list_val": "./data/validation.odgt",
+    "DATASET.num_class": 13,
+    "DATASET.imgSizes": IMG_SIZES,
+    "DATASET.imgMaxSize": IMG_MAX_SIZE,
+    "DATASET.padding_constant": PADDING_CONSTANT,
+    "DIR": "ckpt/ade20k-resnet50dilated-ppm_deepsup",
+    "VAL.checkpoint": "epoch_20.pth",
+}
+
+
+def _decode_value(v):
+    """yacs' _decode_cfg_value: strings that are Python literals become those literals"""
+    if isinstance(v, str):
+        try:
+            return ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            return v
+    return v
+
+
+def load_cfg(cfg_file, overrides):
+    """Flat "SECTION.key" -> value: the defaults, then the yaml file (read only when given), then KEY VALUE pairs."""
+    cfg = dict(CFG_DEFAULTS)
+    if cfg_file:
+        import yaml
+        with open(cfg_file) as f:
+            tree = yaml.safe_load(f) or {}
+
+        def walk(node, prefix):
+            for k, v in node.items():
+                if isinstance(v, dict):
+                    walk(v, prefix + k + ".")
+                else:
+                    cfg[prefix + k] = _decode_value(v)
+        walk(tree, "")
+    if len(overrides) % 2:
+        raise SystemExit("overrides come in KEY VALUE pairs: %r" % (overrides,))
+    for k, v in zip(overrides[0::2], overrides[1::2]):
+        cfg[k] = _decode_value(v)
+    return cfg
 
 
 def main():
@@ -86,18 +145,32 @@ def main():
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f16x2", "f32x3"],
                    help="bf16: bf16 storage (throughput mode); f32: exact fp32 MFMA (the reference's arithmetic); f16x2 / f32x3: fp32 tensors with the convolution products on the fp16 / bf16 matrix cores (fp32-accurate splits, bench.py's headline is f16x2)")
     p.add_argument("--synthetic", action="store_true")
+    p.add_argument("--cfg", default="", metavar="FILE", help="yaml config of the reference (read only when given)")
+    p.add_argument("--gpu", type=int, default=0, help="gpu to use")
+    p.add_argument("--workers", type=int, default=0,
+                   help="decode threads of the real-data run (default: min(16, CPUs this process may use))")
+    p.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides (real-data run)")
     opts = p.parse_args()
-    if not opts.synthetic:
-        raise SystemExit("only --synthetic frames are available (dataset decoding is outside the hot path)")
-    device = torch.device("cuda", 0)
+    device = torch.device("cuda", opts.gpu)
     torch.cuda.set_device(device)
     torch.manual_seed(304)
-    enc = models.ModelBuilder.build_encoder("resnet50dilated", fc_dim=2048, weights=opts.encoder_weights)
-    dec = models.ModelBuilder.build_decoder("ppm_deepsup_embedding", fc_dim=2048, num_class=13,
-                                            weights=opts.decoder_weights, use_softmax=True)
+    cfg = None if opts.synthetic else load_cfg(opts.cfg, opts.opts)
+    num_class = 13 if cfg is None else int(cfg["DATASET.num_class"])
+    enc_w, dec_w = opts.encoder_weights, opts.decoder_weights
+    if cfg is not None:
+        enc_w = enc_w or os.path.join(cfg["DIR"], "encoder_" + cfg["VAL.checkpoint"])
+        dec_w = dec_w or os.path.join(cfg["DIR"], "decoder_" + cfg["VAL.checkpoint"])
+        if not (os.path.exists(enc_w) and os.path.exists(dec_w)):
+            raise SystemExit("checkpoint does not exist: %s / %s" % (enc_w, dec_w))
+    enc = models.ModelBuilder.build_encoder("resnet50dilated", fc_dim=2048, weights=enc_w)
+    dec = models.ModelBuilder.build_decoder("ppm_deepsup_embedding", fc_dim=2048, num_class=num_class,
+                                            weights=dec_w, use_softmax=True)
     seg = models.SegmentationModuleOOD(enc, dec, None).to(device).eval()
     seg.set_compute_dtype(torch.bfloat16 if opts.dtype == "bf16" else torch.float32,
                             fp32_products={"f32": "exact", "f32x3": "bf16x3", "f16x2": "f16x2"}.get(opts.dtype))
+    if cfg is not None:
+        run_dataset(seg, cfg, opts, num_class, device)
+        return
     g = torch.Generator().manual_seed(7)
     shapes = resized_shapes(opts.height, opts.width)
 
@@ -112,6 +185,28 @@ def main():
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])          # :587-589
     print("Mean IoU: %.4f, Accuracy: %.2f%%, Inference Time: %.4fs" % (r["seg"]["Mean IoU"], 100.0 * r["seg"]["Overall Acc"],
                                                                         r["sec_per_frame"]))
+
+
+def run_dataset(seg, cfg, opts, num_class, device):
+    """The reference's `main` + summary (eval_ood_traditional.py:520-560,563-600) on a StreetHazards-layout tree."""
+    from datasets.streethazards import StreetHazardsReader
+    reader = StreetHazardsReader(cfg["DATASET.root_dataset"], cfg["DATASET.list_val"],
+                                 img_sizes=tuple(cfg["DATASET.imgSizes"]), img_max_size=cfg["DATASET.imgMaxSize"],
+                                 padding_constant=cfg["DATASET.padding_constant"], workers=opts.workers or None,
+                                 device=device)
+    print("# samples: {}".format(len(reader)))
+    tic = time.perf_counter()
+    r = evaluate(seg, reader, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back)
+    wall = time.perf_counter() - tic
+    for i, iou in enumerate(r["known_iou"]):
+        print("class [{}], IoU: {:.4f}".format(i, iou))
+    print("[Eval Summary]:")
+    print("Mean IoU: {:.4f}, Accuracy: {:.2f}%, Inference Time: {:.4f}s"
+          .format(r["known_iou"].mean(), 100.0 * r["seg"]["Overall Acc"], r["sec_per_frame"]))
+    print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])
+    print("Wall clock: {:.2f} frames/s ({} frames, {} decode workers); model only: {:.2f} frames/s"
+          .format(len(reader) / wall, len(reader), reader.workers, 1.0 / r["sec_per_frame"]))
+    print("Evaluation Done!")
 
 
 if __name__ == "__main__":
