@@ -3,15 +3,21 @@
 distance head + DML loss + SGD), synthetic 768x768 crops, 16 images per GPU (BASELINE.json configs[2];
 configs[3] when launched on 8 ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--batch 16] [--size 768] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--batch 16] [--size 768] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` = global images / (max-over-ranks wall time of exactly K steps),
-inputs resident in HBM.  `roofline` = the dominant kernel class (implicit-GEMM convolution on MFMA):
-algorithmic conv FLOPs of one step / summed duration of its conv launches, measured with HIP events on the
-launch stream in a separate profiled pass right after the timed region.  `cpu_baseline` = the CPU oracle
-(a PyTorch restatement of the reference, kind "port") timed on this box's host cores on a bounded sample.
+inputs resident in HBM.  A plain run does only what that figure needs: set up, W warm-up steps, the K timed steps,
+--dump-outputs if given, the line.  Everything else is measured only with --full:
+  `roofline` = the dominant kernel class (implicit-GEMM convolution on MFMA): algorithmic conv FLOPs of one step /
+  summed duration of its conv launches, measured with HIP events on the launch stream in a separate profiled pass
+  right after the timed region (also in --mode infer / fwd);
+  `host_enqueue_ms_per_step`, `hbm_kernel`, `input_pipeline`, the bf16 / exact-fp32 / three-term companions;
+  `cpu_baseline` = the CPU oracle (a PyTorch restatement of the reference, kind "port") timed on this box's host cores
+  on a bounded sample;
+  with several ranks, the 32 MB all-reduce self-diagnosis (`config.allreduce_32mb_*`).
+--no-profile, --no-companions and --no-cpu-baseline leave parts of that out of a --full run.
 """
 import argparse
 import json
@@ -625,7 +631,7 @@ def infer_bench(args):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {"logits": preds, "features": score} if fwd_only else {"preds": preds, "score": score})
     roof = None
-    if rank == 0 and world == 1 and not args.no_profile:
+    if args.full and rank == 0 and world == 1 and not args.no_profile:
         # every conv launch of the (un-forked) forward plan alone on the stream, HIP events around each: algorithmic FLOPs / summed time
         plan = next(iter(model._engine.plans.values()))
         flops, _ = conv_flops_of_plan(plan)
@@ -717,12 +723,17 @@ def main():
                          "split; bf16 = bf16 storage (the throughput mode: statistically gated, not a 1e-3 mode)")
     ap.add_argument("--batch", type=int, default=16, help="images per GPU")
     ap.add_argument("--size", type=int, default=768)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the profiled conv pass (roofline), host enqueue "
+                         "time, the distance kernel, the input pipeline, the bf16 / exact-fp32 / three-term companions, the CPU "
+                         "baseline, the all-reduce self-diagnosis of a multi-rank run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="--full without the profiled conv pass, the distance kernel, the input pipeline and the companions")
     ap.add_argument("--no-fp32-companion", "--no-companions", dest="no_fp32_companion", action="store_true",
-                    help="skip the companion passes (bf16 storage, exact fp32, three-term split) of the default run")
+                    help="--full without the companion passes (bf16 storage, exact fp32, three-term split)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every physical core of the host")
-    ap.add_argument("--dump-conv", default=None, help="write a per-launch conv table (json) from the profiled pass")
+    ap.add_argument("--dump-conv", default=None, help="write a per-launch conv table (json) from the profiled pass (needs --full)")
     ap.add_argument("--mode", default="train", choices=["train", "infer", "fwd", "ood"],
                     help="train = the headline metric (default); infer = SURVEY 8(d) config #5: open-world inference "
                          "at --height x --width, --batch images per step (default 1), scores on the device; fwd = BASELINE "
@@ -736,6 +747,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.dump_conv and not args.full:
+        ap.error("--dump-conv needs --full (the profiled conv pass)")
     if args.print_csrc_sha:
         print(csrc_sha())
         return
@@ -756,8 +769,8 @@ def main():
     backend = dist.get_backend() if dp else None
 
     res = train_pass(args, args.dtype, device, rank, world, steps=args.steps, warmup=args.warmup,
-                     profile=(world == 1 and not args.no_profile), dump_conv=args.dump_conv,
-                     dump_dir=args.dump_outputs if rank == 0 else None)
+                     profile=(args.full and world == 1 and not args.no_profile), dump_conv=args.dump_conv,
+                     dump_dir=args.dump_outputs if rank == 0 else None, extras=args.full)
     out = None
     if rank == 0:
         out = {"metric": "images/sec train-step, DeepLabV3+R101 768x768 bs=16; % HBM & MFMA roofline",
@@ -770,8 +783,9 @@ def main():
                           "arithmetic": ARITHMETIC[args.dtype],
                           "global_batch": args.batch * world, "parallelism": "dp%d" % world,
                           "rccl_ranks": dist.get_world_size() if dp else 1, "backend": backend,
-                          "final_loss": res["final_loss"]},
-               "host_enqueue_ms_per_step": res["host_ms"]}
+                          "final_loss": res["final_loss"]}}
+        if "host_ms" in res:
+            out["host_enqueue_ms_per_step"] = res["host_ms"]
         for k in ("allreduce_32mb_ms", "allreduce_32mb_busbw_GBps"):
             if k in res:
                 out["config"][k] = res[k]
@@ -779,7 +793,7 @@ def main():
             out["config"]["allreduce_backend"] = backend      # (gloo: host copies, says nothing about the fabric)
         if "roofline" in res:
             out["roofline"] = res["roofline"]
-    if world == 1 and not args.no_profile:
+    if args.full and world == 1 and not args.no_profile:
         out["hbm_kernel"] = bench_distance_kernel(args.batch, args.size, device)
         dpath = os.path.join(ROOT, "profiles", ROUND + "_traffic_dist_pmc.json")          # tools/run_traffic_dist.sh
         if os.path.exists(dpath) and args.batch == 16 and args.size == 768:
@@ -820,7 +834,7 @@ def main():
             f3 = train_pass(args, "f32x3", device, rank, world, steps=max(4, args.steps // 2), warmup=2, profile=False, dump_conv=None)
             out["fp32_exact_companion"]["three_term_split"] = {"dtype": "f32x3", "value": f3["value"], "ms_per_step": f3["ms_per_step"],
                                                                "final_loss": f3["final_loss"]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.size, args.cpu_threads)
         if "input_pipeline" in out:
             out["input_pipeline"]["cpu_baseline"] = cpu_input_pipeline(args.size)
@@ -831,10 +845,11 @@ def main():
         dist.destroy_process_group()
 
 
-def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_conv=None, dump_dir=None):
+def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_conv=None, dump_dir=None, extras=True):
     """W warm-up + exactly K timed train steps in `dtype` (barrier + synchronize on both sides, max over ranks), then --
     single GPU only -- the profiled conv pass.  `dump_dir`: the last timed step's loss, logits, prototypes, features and the
-    model state after its optimizer step go there (dump_outputs).  The model and its plans are released on return."""
+    model state after its optimizer step go there (dump_outputs).  `extras`: also the all-reduce self-diagnosis (several
+    ranks) and the host enqueue probes.  The model and its plans are released on return."""
     from dmlnet import parallel
     import network
     import utils
@@ -875,7 +890,7 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         loss = step()
     torch.cuda.synchronize()
     ar_ms = None
-    if dp:
+    if dp and extras:
         # self-diagnosis for the first multi-GPU run (outside the timed region): one gradient bucket's worth of all-reduce on
         # the reducer's communication stream.  bus bandwidth = 2 (n - 1) / n x bytes / time: ~150-250 GB/s says RCCL runs over
         # xGMI, a few GB/s says it fell back to host memory (DESIGN.md section 6 states what the step should then look like)
@@ -894,6 +909,7 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         torch.cuda.synchronize()
         ar_ms = e0.elapsed_time(e1) / 5
         del buf
+    if dp:
         dist.barrier()
     torch.cuda.synchronize()
     last = {} if dump_dir else None
@@ -914,17 +930,19 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         last["state"] = torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()])
         dump_outputs(dump_dir, last)
         del last
-    # host time to ENQUEUE one step (outside the timed region): the queue is drained first, so the launches never wait
-    # for the GPU and what is measured is the host's own work (Python + the native launch-list replay + HIP launches)
-    host = 0.0
-    for _ in range(3):
+    res = {"value": args.batch * world * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "final_loss": final_loss}
+    n_probe = 3 if extras else 0
+    if extras:
+        # host time to ENQUEUE one step (outside the timed region): the queue is drained first, so the launches never wait
+        # for the GPU and what is measured is the host's own work (Python + the native launch-list replay + HIP launches)
+        host = 0.0
+        for _ in range(n_probe):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            step()
+            host += time.perf_counter() - h0
         torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        step()
-        host += time.perf_counter() - h0
-    torch.cuda.synchronize()
-    res = {"value": args.batch * world * steps / elapsed, "ms_per_step": elapsed / steps * 1e3,
-           "final_loss": final_loss, "host_ms": host / 3 * 1e3}
+        res["host_ms"] = host / n_probe * 1e3
     if ar_ms is not None:
         n = dist.get_world_size()
         res["allreduce_32mb_ms"] = ar_ms
@@ -933,7 +951,7 @@ def train_pass(args, dtype, device, rank, world, steps, warmup, profile, dump_co
         # the conv launches of a step in issue order, for tools/pmc_by_class.py (profiler runs)
         plan = next(p for k, p in model._engine.plans.items() if k[4])
         with open(os.environ["DML_BENCH_OPLOG"], "w") as fh:
-            json.dump({"dtype": dtype, "steps_in_run": warmup + steps + 3, "ops": conv_op_list(plan)}, fh)
+            json.dump({"dtype": dtype, "steps_in_run": warmup + steps + n_probe, "ops": conv_op_list(plan)}, fh)
     if profile:
         plan = next(p for k, p in model._engine.plans.items() if k[4])
         flops, _ = conv_flops_of_plan(plan)

@@ -206,6 +206,18 @@ def test_committed_bench_line_carries_the_contract_fields():
     assert d["host_enqueue_ms_per_step"] > 0
 
 
+def test_bench_full_option_and_its_guard():
+    """bench.py has --full (everything beside the headline figure); --dump-conv, which needs the profiled pass, is refused
+    without it before anything touches a GPU."""
+    import subprocess
+    import sys
+    bench = os.path.join(H.ROOT, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, cwd=H.ROOT, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    r = subprocess.run([sys.executable, bench, "--dump-conv", "conv.json"], capture_output=True, text=True, cwd=H.ROOT, timeout=300)
+    assert r.returncode == 2 and "--dump-conv needs --full" in r.stderr, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_native_plan_packing_and_dispatch_without_a_gpu():
     """dml_plan_run / DmlPlanOp on the host side only: entry-point ids, argument packing (pointers, negative ints,
     floats, doubles, by-reference descriptors, indirect int32), write-through of per-step argument patches, and the

@@ -174,7 +174,7 @@ def test_bench_gpus_flag_launches_ranks_itself():
     DML_BENCH_ALLOW_SHARED_GPU=1 (test hook: ranks share device 0 over gloo) it must print ONE line with n_gpus 2."""
     import json
     args = [sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "2", "--size", "128", "--batch", "2", "--steps", "2",
-            "--warmup", "1", "--no-cpu-baseline"]
+            "--warmup", "1", "--full", "--no-cpu-baseline"]
     if __import__("torch").cuda.device_count() < 2:
         r = subprocess.run(args, capture_output=True, text=True, cwd=H.ROOT, timeout=600)
         assert r.returncode != 0 and "GPU" in (r.stderr + r.stdout)
@@ -191,11 +191,11 @@ def test_bench_gpus_flag_launches_ranks_itself():
 
 
 def test_bench_script_default_path_small():
-    """bench.py end to end (timed region, profiled conv pass, distance kernel, input pipeline) at a small size: the
-    JSON line must carry the contract's fields."""
+    """bench.py --full end to end (timed region, profiled conv pass, distance kernel, input pipeline, companions) at a small
+    size: the JSON line must carry the contract's fields."""
     import json
     r = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--size", "128", "--batch", "2", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, cwd=H.ROOT, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, cwd=H.ROOT, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -210,7 +210,7 @@ def test_bench_script_default_path_small():
     assert d["bf16_companion"]["value"] > 0 and d["bf16_companion"]["roofline"]["achieved"] > 0
     assert d["fp32_exact_companion"]["value"] > 0 and d["fp32_exact_companion"]["three_term_split"]["value"] > 0
     r = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--mode", "infer", "--height", "128", "--width",
-                        "256", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, cwd=H.ROOT, timeout=900)
+                        "256", "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, cwd=H.ROOT, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     di = json.loads(r.stdout.strip().splitlines()[-1])
     assert di["value"] > 0 and di["dtype"] == "f16x2" and di["roofline"]["achieved"] > 0
@@ -219,6 +219,36 @@ def test_bench_script_default_path_small():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     df = json.loads(r.stdout.strip().splitlines()[-1])
     assert df["value"] > 0 and df["dtype"] == "bf16" and "forward-only" in df["metric"]
+
+
+def test_bench_plain_run_is_lean_and_computes_what_full_does(tmp_path):
+    """bench.py without --full: the contract's fields and nothing measured beside the timed steps; the last timed step's
+    outputs (--dump-outputs) equal element for element those of a --full run with the same arguments."""
+    import json
+    base = [sys.executable, os.path.join(H.ROOT, "bench.py"), "--size", "128", "--batch", "2", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-companions"])):
+        r = subprocess.run(base + ["--dump-outputs", str(tmp_path / tag)] + extra, capture_output=True, text=True, cwd=H.ROOT,
+                           timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        out = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(out) == 1, out
+        lines[tag] = json.loads(out[0])
+    p, f = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in p, k
+    assert p["value"] > 0 and p["dtype"] == "f16x2" and p["metric"] == f["metric"] and p["unit"] == f["unit"]
+    for k in ("roofline", "hbm_kernel", "input_pipeline", "host_enqueue_ms_per_step", "bf16_companion", "fp32_exact_companion",
+              "value_fp32_exact", "cpu_baseline"):
+        assert k not in p, k
+    assert "roofline" in f and "hbm_kernel" in f and "host_enqueue_ms_per_step" in f
+    assert p["config"]["final_loss"] == f["config"]["final_loss"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.shape == b.shape and np.array_equal(a, b), n
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "f16x2"])

@@ -3,8 +3,8 @@
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/fuse_ab
 rm -rf $OUT; mkdir -p $OUT
-python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --dump-conv $OUT/conv_fused.json > $OUT/fused.json 2>/dev/null
-DML_FUSE_BN_REDUCE=0 python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --dump-conv $OUT/conv_unfused.json > $OUT/unfused.json 2>/dev/null
+python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --dump-conv $OUT/conv_fused.json > $OUT/fused.json 2>/dev/null
+DML_FUSE_BN_REDUCE=0 python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --dump-conv $OUT/conv_unfused.json > $OUT/unfused.json 2>/dev/null
 python3 - <<PY
 import json,collections
 for tag in ("fused","unfused"):

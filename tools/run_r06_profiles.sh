@@ -20,9 +20,9 @@ stats() {      # stats <dir> <dest.csv>
   [ -n "$f" ] || { echo "no kernel_stats.csv under $1" >&2; exit 1; }
   cp "$f" "$2"; rm -rf "$1"
 }
-HB="$R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile --no-companions"
-B="$R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-profile --no-companions"
-python3 $R/bench.py --dump-conv $OUT/conv_table.json > $OUT/bench.json 2> $OUT/bench.err
+HB="$R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-profile --no-companions"
+B="$R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-profile --no-companions"
+python3 $R/bench.py --full --dump-conv $OUT/conv_table.json > $OUT/bench.json 2> $OUT/bench.err
 last_json $OUT/bench.json
 # per-kernel time of the headline command: weight gradients on the side stream (as timed) and serial (un-contended)
 for mode in 1 0; do
@@ -67,13 +67,13 @@ rm -rf $OUT/rd $OUT/wr
 # #2 forward-only 768 x 768 x 8 bf16 -- each with the conv roofline of its forward plan
 for cfg in "infer f16x2 1" "infer f16x2 4" "infer bf16 1" "infer bf16 4" "fwd bf16 8" "fwd f16x2 8"; do
   set -- $cfg
-  python3 $R/bench.py --mode $1 --dtype $2 --batch $3 --steps 20 --warmup 5 2> /dev/null | grep "^{" > $OUT/bench_$1_$2_b$3.json
+  python3 $R/bench.py --mode $1 --dtype $2 --batch $3 --steps 20 --warmup 5 --full 2> /dev/null | grep "^{" > $OUT/bench_$1_$2_b$3.json
   valid_json $OUT/bench_$1_$2_b$3.json
 done
 # the bench line again with this run's PMC summaries in place (bench.py quotes `traffic` only from files whose csrc_sha matches)
 cp $OUT/traffic_pmc.json $R/profiles/r06_traffic_pmc.json; cp $OUT/bf16_traffic_pmc.json $R/profiles/r06_bf16_traffic_pmc.json
 cp $OUT/traffic_dist_pmc.json $R/profiles/r06_traffic_dist_pmc.json
-python3 $R/bench.py --dump-conv $OUT/conv_table_final.json > $OUT/bench_final.json 2> $OUT/bench_final.err
+python3 $R/bench.py --full --dump-conv $OUT/conv_table_final.json > $OUT/bench_final.json 2> $OUT/bench_final.err
 last_json $OUT/bench_final.json
 find $OUT -name "*.log" -size +200k -delete
 ls -la $OUT

@@ -7,8 +7,8 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/traffic
 rm -rf $OUT; mkdir -p $OUT
 SHA=$(python3 $R/bench.py --print-csrc-sha)
-DML_OVERLAP_WGRAD=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/rd -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile > $OUT/rd.log 2>&1
-DML_OVERLAP_WGRAD=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/wr -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile > $OUT/wr.log 2>&1
+DML_OVERLAP_WGRAD=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/rd -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-profile > $OUT/rd.log 2>&1
+DML_OVERLAP_WGRAD=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/wr -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-profile > $OUT/wr.log 2>&1
 # steps seen by the profiler: 1 warm-up + 2 timed + 3 host-enqueue probes
 python3 $R/tools/traffic_summary.py $OUT/rd $OUT/wr 6 $SHA > $OUT/traffic.json 2> $OUT/summary.err
 rm -rf $OUT/rd $OUT/wr
