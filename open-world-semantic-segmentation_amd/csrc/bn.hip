@@ -1166,9 +1166,7 @@ extern "C" int dml_bn_bwd_apply(const void* dz, const void* y, const void* z, co
     // workgroup to retire (in the overlapped trace this kernel lasted 175 us per launch against 66 alone); one-wave blocks start at
     // once, two per CU: 80.35 -> 79.15 ms per step, alone unchanged (profiles/r05_ab_bn_bwd_one_wave_blocks.txt).  The bf16 step, whose
     // convolution workgroups are not persistent, gains 0.5 % from the same geometry (40.06 -> 39.87 ms).
-    // DML_BN_BWD_THREADS=256: the old geometry (A/B)
-    static const int bt_env = getenv("DML_BN_BWD_THREADS") ? atoi(getenv("DML_BN_BWD_THREADS")) : 64;
-    const int bt = (bt_env == 64 || bt_env == 128 || bt_env == 256) ? bt_env : 256;
+    constexpr int bt = 64;
     if (dtype == DML_F32 && planes && !dy && !amax && (mask || !relu) && (N & 7) == 0 && (lddz & 3) == 0 && (ldy & 3) == 0 &&
         (ldp & 7) == 0 && (plane_stride & 7) == 0 && (!dres || (lddres & 3) == 0) &&
         ((reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(y) |

@@ -35,7 +35,7 @@ struct ConvArgs {
     int y_f32, accum;
     int nblk_n, nblk_m;
     FastDiv div_wo, div_howo, div_c;
-    float* dbg;      // tuning builds only (ABL == 3): per-wave phase timings
+    float* unused0_;             // unused0_ / unused1_: unused, they keep the layout and with it the kernels' code as it was
     uint32_t x_bytes, w_bytes;   // operand extents for the buffer descriptors (fast path: both < 2^31)
     int w_tiled;                 // weights in the tile-major layout (DmlConvDesc::w_tiled): LDS-DMA kernels only
     int ws_min_tiles;            // DmlConvDesc::ws_min_tiles
@@ -75,7 +75,7 @@ struct ConvArgs {
     int f32_split;      // fp32 tensors: products through the three-term bf16 split (DmlConvDesc::f32_split)
     // bit 0: the epilogue's bf16 output stores carry the non-temporal hint, bit 1: its partial-statistics stores (launch_conv)
     int nt_out;
-    int half_stagger;      // conv_ws_half_kernel: start delay of a CU's second workgroup, 10 ns ticks (launch_conv)
+    int unused1_;
     // one parity class of a stride-2 data gradient as a stride-1 launch on dY's grid (DmlConvDesc::sub_grid): the launch's rows are
     // the pixels (b, 2 y2 + sub_y, 2 x2 + sub_x) of the B x 2 Ho x 2 Wo tensors y / res_dz / bnr_y / masks (ws_out_row)
     int pad_x;             // padding along the width (== pad unless DmlConvDesc::pad_w_set)
@@ -496,7 +496,7 @@ __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[NT][MT], const ConvAr
 // ------------------------------------------------------------------------------------------------
 // forward / data-gradient kernel
 // ------------------------------------------------------------------------------------------------
-template <typename T, int BN, bool ALIGNED, int MODE, int ABL = 0>   // ABL: tuning ablations (tools/bench_conv.py)
+template <typename T, int BN, bool ALIGNED, int MODE>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) void conv_igemm_kernel(const ConvArgs a) {
     constexpr int BM = 128;
     constexpr int VEC = Elem<T>::VEC;
@@ -513,8 +513,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    uint64_t t_start = 0;
-    if constexpr (ABL == 3) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_start)::"memory");
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     const int blk_m = tile / a.nblk_n, blk_n = tile - blk_m * a.nblk_n;
     const int m0 = blk_m * BM, n0 = blk_n * BN;
@@ -599,9 +597,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
     uint4 a_reg[A_LD], b_reg[B_LD];
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
-    int c0_staged = 0;          // channel offset of the tile currently held in a_reg (ABL == 4 only)
     auto load_tiles = [&](int kt, int tap_r, int tap_s, int c0) {
-        c0_staged = c0;
         if constexpr (ALIGNED) {
             const uint32_t tapbit = 1u << (tap_r * a.S + tap_s);
             const int soff = tap_delta(tap_r, tap_s) + c0 * ES;
@@ -668,27 +664,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
         }
     };
     auto store_tiles = [&](int buf) {
-        if constexpr (ABL == 4 && sizeof(T) == 2) {
-            // feasibility probe for "normalise on load" (DESIGN.md, next round): a per-channel affine + ReLU applied to the
-            // activation tile between its global load and the LDS write, as a consumer conv would apply the producer's
-            // BatchNorm instead of reading a normalised copy.  Padding stays zero (all-zero pieces are left alone).
-            const int cb = (c0_staged + kvec * VEC) % a.C;
-            float sc[8], sh[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { sc[e] = a.bnr_mean[cb + e]; sh[e] = a.bnr_invstd[cb + e]; }      // probe: fields unused in forward mode
-#pragma unroll
-            for (int j = 0; j < A_LD; ++j) {
-                uint32_t u[4] = {a_reg[j].x, a_reg[j].y, a_reg[j].z, a_reg[j].w};
-                const bool pad = (u[0] | u[1] | u[2] | u[3]) == 0u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float lo = fmaxf(fmaf(__uint_as_float(u[e] << 16), sc[2 * e], sh[2 * e]), 0.f);
-                    const float hi = fmaxf(fmaf(__uint_as_float(u[e] & 0xffff0000u), sc[2 * e + 1], sh[2 * e + 1]), 0.f);
-                    u[e] = pad ? 0u : pack_bf16x2(lo, hi);
-                }
-                a_reg[j] = make_uint4(u[0], u[1], u[2], u[3]);
-            }
-        }
 #pragma unroll
         for (int j = 0; j < A_LD; ++j) {
             const int row = prow + j * RPP;
@@ -726,28 +701,12 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
 
     const int lr = lane & 15, lq = lane >> 4;
     int cur = 0;
-    // ABL == 3: s_memtime stamps at the points where lgkmcnt(0) is harmless; deltas averaged over the K loop
-    uint32_t ph[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t tprev = 0;
-    auto stamp = [&](int i) {
-        if constexpr (ABL == 3) {
-            uint64_t t;
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (i >= 0) ph[i] += (uint32_t)(t - tprev);
-            tprev = t;
-        }
-    };
-    stamp(-1);
-    const uint64_t t_loop = tprev;
     for (int kt = 0; kt < KT; ++kt) {
         const bool has_next = kt + 1 < KT;
-        if (has_next && ABL != 1) {
+        if (has_next) {
             advance();
             load_tiles(kt + 1, tap_r, tap_s, c0);
         }
-        stamp(0);      // global loads issued
         const T* as = As(cur) + (wm * TM) * BK;
         const T* bs = Bs(cur) + (wn * TN) * BK;
         if constexpr (sizeof(T) == 2) {
@@ -760,19 +719,11 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
                 const int row = j * 16 + lr;
                 af[j] = *reinterpret_cast<const mfma_bf16x8*>(as + row * BK + swz_chunk<T>(row, lq) * 8);
             }
-            stamp(1);  // fragments in registers
-            if constexpr (ABL == 2) {
 #pragma unroll
-                for (int i = 0; i < NT; ++i) asm volatile("" ::"v"(bf[i]));
+            for (int i = 0; i < NT; ++i)
 #pragma unroll
-                for (int j = 0; j < MT; ++j) asm volatile("" ::"v"(af[j]));
-            } else {
-#pragma unroll
-                for (int i = 0; i < NT; ++i)
-#pragma unroll
-                    for (int j = 0; j < MT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[i], af[j], acc[i][j], 0, 0, 0);
-            }
+                for (int j = 0; j < MT; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[i], af[j], acc[i][j], 0, 0, 0);
         } else {
 #pragma unroll
             for (int kk = 0; kk < BK / 4; ++kk) {
@@ -791,16 +742,10 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[i], af[j], acc[i][j], 0, 0, 0);
             }
         }
-        stamp(2);      // MFMAs issued
-        if constexpr (ABL == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(3);      // next tile arrived in registers
         if (has_next) store_tiles(cur ^ 1);
-        stamp(4);      // LDS writes drained
         __syncthreads();
-        stamp(5);      // barrier released
         cur ^= 1;
     }
-    const uint64_t t_end_loop = tprev;
 
     // Cut the accumulators' live ranges here: without it hipcc keeps the MFMA results un-tied through the
     // branchy epilogue and re-copies all 64 AGPRs (v_accvgpr_mov + s_nop) in EVERY K step (-35 % throughput).
@@ -809,17 +754,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(3))) v
 #pragma unroll
         for (int j = 0; j < MT; ++j) asm volatile("" : "+v"(acc[i][j]));
     conv_epilogue<T, NT, MT, MODE>(acc, a, m0 + wm * TM, n0 + wn * TN, lr, lq);
-    if constexpr (ABL == 3) {
-        uint64_t t_end;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_end)::"memory");
-        if (a.dbg != nullptr && lane == 0) {
-            float* o = a.dbg + ((int64_t)blockIdx.x * 4 + wave) * 8;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) o[i] = (float)ph[i] / (float)KT;
-            o[6] = (float)(uint32_t)(t_loop - t_start);
-            o[7] = (float)(uint32_t)(t_end - t_end_loop);
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1049,8 +983,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // TMW = 128 (with BM = 256): 4 waves (2 x 2) on a 128 x 64 WAVE tile -- 32 MFMAs per wave and K step against 12 KB of
 // fragment reads (the 64 x 64 wave tile: 16 against 8 KB), half the barriers per FLOP; 128 accumulator registers, two
 // workgroups per CU = two waves per SIMD.
-// PH (tuning builds only, dml_debug_conv_ablate 5): s_memtime stamps around the phases of a K step, per-wave sums to a.dbg
-template <int BN, int MODE, int NST, int WPE = 3, int BM = 128, int TMW = 64, bool PH = false>
+template <int BN, int MODE, int NST, int WPE = 3, int BM = 128, int TMW = 64>
 __global__ __launch_bounds__(BM / TMW * 128) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_igemm_dma_kernel(const ConvArgs a, const uint32_t x_bytes,
                                                                   const uint32_t w_bytes) {
     typedef bf16_t T;
@@ -1183,22 +1116,13 @@ __global__ __launch_bounds__(BM / TMW * 128) __attribute__((amdgpu_waves_per_eu(
         if (t < KT) issue(kbeg + t, t);
 
     const int lr = lane & 15, lq = lane >> 4;
-    uint64_t ph_t[5] = {0, 0, 0, 0, 0}, ph_sum[4] = {0, 0, 0, 0}, ph_begin = 0;
-    auto stamp = [&](int i) {
-        if constexpr (PH) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ph_t[i])::"memory");
-    };
-    if constexpr (PH) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ph_begin)::"memory");
     for (int kt = 0; kt < KT; ++kt) {
-        stamp(0);
         // tiles kt .. min(kt + LA - 1, KT - 1) are in flight; tile kt must have landed
         if (LA > 2 && kt + 2 < KT) wait_vmcnt<(LA > 2 ? 2 : 0) * NI>();
         else if (LA > 1 && kt + 1 < KT) wait_vmcnt<(LA > 1 ? 1 : 0) * NI>();
         else wait_vmcnt<0>();
-        stamp(1);
         __builtin_amdgcn_s_barrier();
-        stamp(2);
         if (kt + LA < KT) issue(kbeg + kt + LA, (kt + LA) % NST);
-        stamp(3);
         const T* as = smem + (kt % NST) * STAGE + (wm * TM) * BK;
         const T* bs = smem + (kt % NST) * STAGE + BM * BK + (wn * TN) * BK;
         mfma_bf16x8 bf[NT], af[MT];
@@ -1215,27 +1139,6 @@ __global__ __launch_bounds__(BM / TMW * 128) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
             for (int j = 0; j < MT; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[i], af[j], acc[i][j], 0, 0, 0);
-        if constexpr (PH) {
-            stamp(4);          // (after the MFMAs were ISSUED: the matrix pipe may still be working)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) ph_sum[q] += ph_t[q + 1] - ph_t[q];
-        }
-    }
-    if constexpr (PH) {
-        uint64_t ph_end;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ph_end)::"memory");
-        if (a.dbg != nullptr && lane == 0) {
-            float* o = a.dbg + ((int64_t)blockIdx.x * WAVES + wave) * 8;
-            const float inv = 1.0f / (float)(KT > 0 ? KT : 1);
-            o[0] = (float)ph_sum[0] * inv;      // vmcnt wait
-            o[1] = (float)ph_sum[1] * inv;      // barrier
-            o[2] = (float)ph_sum[2] * inv;      // DMA issue
-            o[3] = (float)ph_sum[3] * inv;      // fragment reads + MFMA issue
-            o[4] = (float)(ph_end - ph_begin) * inv;      // whole loop per step (includes the stamps themselves)
-            o[5] = (float)KT;
-            o[6] = 0.f;
-            o[7] = 0.f;
-        }
     }
     // Cut the accumulators' live ranges here: without it hipcc keeps the MFMA results un-tied through the
     // branchy epilogue and re-copies all 64 AGPRs (v_accvgpr_mov + s_nop) in EVERY K step (-35 % throughput).
@@ -1570,12 +1473,7 @@ __device__ __forceinline__ void conv_epilogue_rows(f32x4 (&acc)[NT][3], const Co
 // (its masks and its first group).  Here every row quad has its own operand registers (a ring of 12, indices compile-time in the
 // unrolled quad loop), the loads run WS_EPI_P quads ahead ACROSS the sub-tile boundaries of the rolled sub-tile loop, and the masks
 // of sub-tile h + 1 are fetched during sub-tile h.
-#ifndef DML_WS_EPI_P
-#define DML_WS_EPI_P 8
-#endif
-#ifndef DML_WS_EPI_OPS
-#define DML_WS_EPI_OPS 1                       // 0: the per-sub-tile pipeline of conv_epilogue_rows for launches with operands too (A/B)
-#endif
+constexpr int WS_EPI_P = 8;
 template <int I, int N, class F>
 __device__ __forceinline__ void ws_static_for(F&& f) {
     if constexpr (I < N) {
@@ -1587,7 +1485,7 @@ template <int NT, int NS, bool HO, bool BNR>
 __device__ __forceinline__ void conv_epilogue_rows_ops(f32x4 (&acc3)[NS][NT][3], const ConvArgs& a, const int mwt, const int nw0,
                                                        const int lane_in, char* stage0, char* stage1, char* mstage) {
     static_assert(NT == 4, "64-channel wave tile");
-    constexpr int P = DML_WS_EPI_P;
+    constexpr int P = WS_EPI_P;
     static_assert(P >= 1 && P <= 11, "ring of 12 row quads");
     typedef unsigned int u32x4_b __attribute__((ext_vector_type(4)));
     constexpr uint32_t OOB = 0x80000000u;
@@ -1803,43 +1701,15 @@ __device__ __forceinline__ void conv_epilogue_rows8(f32x4 (&acc)[NT][3], const C
     chunk(std::integral_constant<int, 5>{});
 }
 
-// timing ablations of the two-plane K loop (tools/build_ablations.sh; never defined in the product build): 1 = no fragment reads in
-// the loop, 2 = no flag polls / waits, 4 = the loaders issue no DMA, 8 = no epilogue (nothing is stored), 16 = no MFMAs.  Results are
-// garbage, durations are what is measured.
-#ifndef DML_WS_ABL
-#define DML_WS_ABL 0
-#endif
-#ifndef DML_WS_SPREAD
-#define DML_WS_SPREAD 1                        // fragment reads of the two-plane K loop between the MFMA quads (0: in front of them)
-#endif
 // (accumulators in the accumulator register file through inline-asm MFMAs were tried in round 5: hipcc splits the 256 registers of a
 // two-waves-per-SIMD kernel 128 / 128, the 144 accumulators of the 144 x 64 wave tile do not fit, and the K loop did not get faster:
 // 888 -> 944 us on the ASPP 3x3, profiles/r05_h2_kloop_ablations.txt)
-#if DML_WS_ABL & 16
-#define WS_MFMA_F16(ACCV, A_, B_) asm volatile("" ::"v"(A_), "v"(B_))
-#else
-#define WS_MFMA_F16(ACCV, A_, B_) ACCV = __builtin_amdgcn_mfma_f32_16x16x32_f16(A_, B_, ACCV, 0, 0, 0)
-#endif
 
 typedef unsigned int u32x4_ws __attribute__((ext_vector_type(4)));
 constexpr int WS_MT = 9;                       // 16-row fragments per wave tile (144 rows)
 constexpr int WS_STAT_ROWS = 48;               // rows per statistics group of this kernel
 constexpr int WS_NST = 6, WS_D = 2;            // ring stages; stages in flight per loader behind the published one
-#ifndef DML_WS_AHEAD
-// activation fragments of the two-plane K loop read this many row groups ahead of their use.  2 (three slots, waits at lgkmcnt 3-6
-// instead of 1-2) measured +-0 on the step, 76.64 vs 76.56 ms over five interleaved pairs: the latency of the fragment reads is covered
-// at one group already; what they cost is issue slots (profiles/r05_h2_kloop_ablations.txt)
-#define DML_WS_AHEAD 1
-#endif
-#ifndef DML_WS_TAP_INNER
-#define DML_WS_TAP_INNER 1                     // K order of the two-plane instantiation: channel groups outermost, taps inside
-#endif
-#ifndef DML_WS_N_FASTEST
-#define DML_WS_N_FASTEST 1                     // tile walk of the two-plane instantiation: column blocks fastest
-#endif
-#ifndef DML_WS_PLANES_NLD
-#define DML_WS_PLANES_NLD 3                    // loader waves of the two-plane instantiation
-#endif
+constexpr int WS_PLANES_NLD = 3;               // loader waves of the two-plane instantiation
 
 // LDS-DMA piece (16 B per lane, 1 KB per wave) from inline asm: m0 = LDS byte address of the piece (wave-uniform), voff per
 // lane, soff scalar; offsets beyond the descriptor write zeros.  Not counted by hipcc: completion by wait_vmcnt only.
@@ -1868,16 +1738,15 @@ __device__ __forceinline__ void ws_st(uint32_t* p, const uint32_t v) { __hip_ato
 // block run rounds apart; PMC: 1x1 256 -> 1024 at 48 x 48 read its input 4.2 x).
 template <int PL>
 __device__ __forceinline__ int ws_tile_m(const int tile, const ConvArgs& a) {
-    return (PL == 2 && DML_WS_N_FASTEST != 0) ? tile / a.nblk_n : tile % a.nblk_m;
+    return PL == 2 ? tile / a.nblk_n : tile % a.nblk_m;
 }
 template <int PL>
 __device__ __forceinline__ int ws_tile_n(const int tile, const ConvArgs& a) {
-    return (PL == 2 && DML_WS_N_FASTEST != 0) ? tile % a.nblk_n : tile / a.nblk_m;
+    return PL == 2 ? tile % a.nblk_n : tile / a.nblk_m;
 }
 
-// ring stages: six in one-plane (bf16) launches, three on two planes (51 KB stages), TWO in the half-tile configuration (two consumer
-// waves, 144 x 128, two workgroups per CU: 2 x 34 KB + flags + staging = 74 KB each)
-constexpr int ws_ring_stages(const int PL, const int NCW) { return PL == 1 ? WS_NST : (NCW == 2 ? 2 : 3); }
+// ring stages: six in one-plane (bf16) launches, three on two planes (51 KB stages)
+constexpr int ws_ring_stages(const int PL) { return PL == 1 ? WS_NST : 3; }
 
 // loader wave LW of NLD: compile-time piece ownership (no branches in the issue loop)
 // PL = 2: every operand tile is two planes (hi, lo fp16 of the scaled fp32 tensor); a stage = [A hi | A lo | B hi | B lo]
@@ -1891,7 +1760,7 @@ __device__ __forceinline__ void conv_ws_loader(const ConvArgs& a, const uint32_t
     constexpr int PA = BM / 16, PB = BN / 16, NP = PL * (PA + PB);
     constexpr int SB = PL * (BM + BN) * BK * 2;
     constexpr int MYP = (NP - LW + NLD - 1) / NLD;
-    constexpr int NST = ws_ring_stages(PL, NCW), D = PL == 1 ? WS_D : 1;
+    constexpr int NST = ws_ring_stages(PL), D = PL == 1 ? WS_D : 1;
     constexpr uint32_t OOB = 0x80000000u;
     static_assert(D * MYP <= 63, "vmcnt is a 6-bit counter");
     // (PL = 2: the descriptors span both planes; the lo plane is reached through the scalar offset)
@@ -1963,7 +1832,7 @@ __device__ __forceinline__ void conv_ws_loader(const ConvArgs& a, const uint32_t
         // outermost a tap sweeps all C channels of that range (4.7 MB at C = 256) before the next tap comes back to the same
         // lines, and every tap was a miss (PMC: 3x3 256 -> 256 at 48 x 48 fetched 4.4 x its algorithmic bytes, the decoder's
         // data gradient 12.6 x).  64 channels = the two K steps that share a 128-byte line.
-        constexpr bool TAPIN = PL == 2 && DML_WS_TAP_INNER != 0;
+        constexpr bool TAPIN = PL == 2;
         const int ksteps_c = a.C / BK;
         int ir = 0, is = 0, ic0 = 0, cg0 = 0;
         for (int kt = 0; kt < KT; ++kt) {
@@ -1997,7 +1866,6 @@ __device__ __forceinline__ void conv_ws_loader(const ConvArgs& a, const uint32_t
 #pragma unroll
             for (int q = 0; q < MYP; ++q) {
                 const int p = q * NLD + LW;
-                if (PL == 2 && (DML_WS_ABL & 4)) continue;
                 if (p < PL * PA) {
                     const uint32_t voff = (mask[q] & tapbit) ? (uint32_t)(base[q] + soff) : OOB;
                     ws_dma16(rs_x, sbase + p * 1024, voff, p < PA ? 0u : a.x_plane_bytes);
@@ -2039,10 +1907,9 @@ typedef _Float16 mfma_f16x8 __attribute__((ext_vector_type(8)));
 template <int MW, int NW, int MODE, int NLD, int PL, int MT, int EPI>
 __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x_bytes, const uint32_t w_bytes) {
     typedef bf16_t T;
-    static_assert(MW * NW == 4 || (PL == 2 && MW == 1 && NW == 2 && NLD == 2),
-                  "four consumer waves, one per SIMD -- or the half-tile configuration: two consumer + two loader waves, two workgroups per CU");
+    static_assert(MW * NW == 4, "four consumer waves, one per SIMD");
     static_assert(MT % 3 == 0 && MT >= 3, "48-row sub-tiles (statistics groups, row epilogue)");
-    constexpr int NCW = MW * NW, NT = 4, NST = ws_ring_stages(PL, NCW);
+    constexpr int NCW = MW * NW, NT = 4, NST = ws_ring_stages(PL);
     constexpr int BM = 16 * MT * MW, BN = 64 * NW;
     constexpr int SB = PL * (BM + BN) * BK * 2;
     // two planes, 144 x 256: 2 KB of private staging per consumer wave behind the flags (conv_epilogue_rows8); the 288 x 128
@@ -2062,30 +1929,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x
     uint32_t* const consumed = ready + 4;                                          // [4] stages whose reads were issued
 
     const int tid = threadIdx.x, lane = tid & 63;
-    int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid < 16) reinterpret_cast<uint32_t*>(smem + NST * SB)[tid] = 0;
-    if constexpr (NCW == 2) {
-        __syncthreads();
-        // Half-tile configuration: workgroups b and b + grid / 2 share a CU, and the four waves of a workgroup sit on the CU's four
-        // SIMDs in an order that rotates from workgroup to workgroup (tools/probe_wg_placement.hip, profiles/r06_wg_placement.txt).
-        // Roles by SIMD, so that the CU's four consumer waves own a SIMD each: the first workgroup's consumers are its waves on SIMDs
-        // 0 / 1, the second's those on SIMDs 2 / 3.  (Were two waves of a workgroup ever on one SIMD, roles by wave index.)
-        uint32_t hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        const int simd = (int)((hw >> 4) & 3u);
-        uint32_t* const sid = reinterpret_cast<uint32_t*>(smem + NST * SB) + 12;      // [4] (words 0 .. 11: ready / consumed / edone)
-        if (lane == 0) sid[wave] = 1u << simd;
-        __syncthreads();
-        const bool perm = (sid[0] | sid[1] | sid[2] | sid[3]) == 0xfu;
-        const int slot = (blockIdx.x >= (gridDim.x + 1) / 2) ? 1 : 0;
-        if (perm) wave = __builtin_amdgcn_readfirstlane(((simd >> 1) == slot ? 0 : NCW) + (simd & 1));
-        // the second workgroup of a CU starts late, so that its epilogues fall under the first one's K loops and vice versa: left to
-        // themselves the two start together and do the same thing at the same time
-        if (slot == 1 && a.half_stagger > 0) {
-            const uint64_t t0 = wall_clock64();
-            while (wall_clock64() - t0 < (uint64_t)a.half_stagger) __builtin_amdgcn_s_sleep(16);
-        }
-    }
     __syncthreads();
 
     const int ntiles = a.nblk_m * a.nblk_n;
@@ -2122,7 +1967,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x
         asm volatile("" ::: "memory");
     };
     constexpr int A_PLANE = BM * BK * 2, B_PLANE = BN * BK * 2;      // bytes from the hi plane to the lo plane inside a stage
-    constexpr bool EPI_OPS = PL == 2 && MODE == 1 && !PRIV_STAGE && DML_WS_EPI_OPS != 0;
+    constexpr bool EPI_OPS = PL == 2 && MODE == 1 && !PRIV_STAGE;
     static_assert(EPI == 0 || EPI_OPS, "epilogue operands: two-plane data gradients");
     constexpr bool hold2 = EPI != 0 && !priv;
 
@@ -2200,12 +2045,10 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x
             // first eight of step k + 1.  __builtin_amdgcn_sched_barrier pins that order: left to itself hipcc sinks each
             // read to just before its use and waits lgkmcnt(0) there, nine exposed LDS latencies per step (measured: 1.45 us per
             // step against 0.72 of MFMA issue).
-            // read-ahead distance of the activation fragments in row groups, and their slots.  Two groups (~24 MFMAs) on the 144-row
-            // wave tiles; the 48-row ones (three groups per step) keep one: two ahead would read the NEXT stage from group 1 on, before
-            // the poll of that stage has been answered
-            constexpr int AH = (DML_WS_AHEAD == 2 && MT >= 9) ? 2 : 1, NS_A = AH + 1;
-            static_assert(AH == 1 || MT % NS_A == 0, "slot of group j = j % 3 in every step");
-            mfma_f16x8 bhA[NT], bhB[NT], bl[NT], ah[NS_A], al[NS_A];
+            // (two groups ahead -- three slots, waits at lgkmcnt 3-6 instead of 1-2 -- measured +-0 on the step, 76.64 vs 76.56 ms over
+            // five interleaved pairs: the latency of the fragment reads is covered at one group already; what they cost is issue slots,
+            // profiles/r05_h2_kloop_ablations.txt)
+            mfma_f16x8 bhA[NT], bhB[NT], bl[NT], ah[2], al[2];
             uint32_t pl[NLD];
 #define WS_FRAG(p) (*reinterpret_cast<const mfma_f16x8*>(p))
             wait_ready(g + 1);                                      // first K step of the tile: exposed once per tile
@@ -2218,10 +2061,6 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x
                 }
                 ah[0] = WS_FRAG(sb + a_off[0]);
                 al[0] = WS_FRAG(sb + a_off[0] + A_PLANE);
-                if constexpr (AH == 2) {
-                    ah[1] = WS_FRAG(sb + a_off[1]);
-                    al[1] = WS_FRAG(sb + a_off[1] + A_PLANE);
-                }
             }
             auto step = [&](auto pc, mfma_f16x8 (&bc)[NT], mfma_f16x8 (&bn)[NT], const bool has_next, const bool rel) {
                 constexpr int P = decltype(pc)::value;
@@ -2232,103 +2071,59 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x
                 for (int j = 0; j < MT; ++j) {
                     // (positions inside the step: row group 1 / 4 / 5.. of the nine of a 144-row wave tile, 0 / 1 / 2 of a 48-row one)
                     constexpr int JP = MT >= 9 ? 1 : 0, JW = MT >= 9 ? 4 : 1, JB = MT >= 9 ? 5 : MT - 1;
-#if DML_WS_SPREAD
                     // The non-MFMA instructions of a row group SPREAD between its three MFMA quads instead of clustered in front of
                     // them: a wave issues in order, and a cluster of five or six of them (two fragment reads, waits, hazard nops)
                     // outlasts the 16 cycles of the MFMA before it -- the ablations put 25-30 % of the K loop on the fragment reads
                     // although the LDS itself is busy a fifth of the time (profiles/r05_h2_kloop_ablations.txt).
-                    // fragment slots: this group's and the one of the group read ahead (AH = 1: two slots, alternating from step to
-                    // step with P because MT is odd; AH = 2: three slots, slot = j % 3 in every step)
-                    const int CUR = AH == 2 ? j % NS_A : (j + P) & 1, NXT = AH == 2 ? (j + AH) % NS_A : (j + 1 + P) & 1;
+                    // fragment slots: this group's and the one of the group read ahead (two slots, alternating from step to step with
+                    // P because MT is odd)
+                    const int CUR = (j + P) & 1, NXT = (j + 1 + P) & 1;
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int i = 0; i < NT; ++i) WS_MFMA_F16(ACC(i, j), bc[i], ah[CUR]);
+                    for (int i = 0; i < NT; ++i) ACC(i, j) = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[i], ah[CUR], ACC(i, j), 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (j + AH < MT) {
-                        if (!(DML_WS_ABL & 1)) ah[NXT] = WS_FRAG(sb + a_off[(j + AH) % MT]);
-                    } else {
-                        asm volatile("" ::: "memory");
-                        if (!(DML_WS_ABL & 1)) ah[NXT] = WS_FRAG(sn + a_off[(j + AH) % MT]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) WS_MFMA_F16(ACC(i, j), bc[i], al[CUR]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (j + AH < MT) {
-                        if (!(DML_WS_ABL & 1)) al[NXT] = WS_FRAG(sb + a_off[(j + AH) % MT] + A_PLANE);
-                    } else {
-                        asm volatile("" ::: "memory");
-                        // every read of stage g has been issued (the tile's LAST stage is announced after the epilogue, which
-                        // stages the output rows in its slot)
-                        if (j + 1 == MT && (rel || priv)) ws_st(consumed + wave, g + 1);
-                        if (!(DML_WS_ABL & 1)) al[NXT] = WS_FRAG(sn + a_off[(j + AH) % MT] + A_PLANE);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) WS_MFMA_F16(ACC(i, j), bl[i], ah[CUR]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (j == JP && !(DML_WS_ABL & 2)) {     // the next step's poll, answered under the MFMAs
-#pragma unroll
-                        for (int w = 0; w < NLD; ++w) pl[w] = ws_ld(ready + w);
-                    }
-                    if (j == JW && !(DML_WS_ABL & 2)) {
-                        rflag = pl[0];
-#pragma unroll
-                        for (int w = 1; w < NLD; ++w) rflag = min(rflag, pl[w]);
-                        if (has_next) wait_ready(g + 2);
-                    }
-                    if (!(DML_WS_ABL & 1)) {
-                        if (MT >= 9) {                      // the next step's hi weight fragments, one per row group
-                            if (j >= JB && j < JB + NT) bn[j - JB] = WS_FRAG(sn + b_off[j - JB]);
-                        } else if (j == JB) {
-#pragma unroll
-                            for (int i = 0; i < NT; ++i) bn[i] = WS_FRAG(sn + b_off[i]);
-                        }
-                    }
-#else
                     if (j + 1 < MT) {
-                        if (!(DML_WS_ABL & 1)) {
-                            ah[(j + 1 + P) & 1] = WS_FRAG(sb + a_off[j + 1]);
-                            al[(j + 1 + P) & 1] = WS_FRAG(sb + a_off[j + 1] + A_PLANE);
-                        }
+                        ah[NXT] = WS_FRAG(sb + a_off[j + 1]);
+                    } else {
+                        asm volatile("" ::: "memory");
+                        ah[NXT] = WS_FRAG(sn + a_off[0]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) ACC(i, j) = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[i], al[CUR], ACC(i, j), 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j + 1 < MT) {
+                        al[NXT] = WS_FRAG(sb + a_off[j + 1] + A_PLANE);
                     } else {
                         asm volatile("" ::: "memory");
                         // every read of stage g has been issued (the tile's LAST stage is announced after the epilogue, which
                         // stages the output rows in its slot)
                         if (rel || priv) ws_st(consumed + wave, g + 1);
-                        if (!(DML_WS_ABL & 1)) {
-                            ah[(MT + P) & 1] = WS_FRAG(sn + a_off[0]);
-                            al[(MT + P) & 1] = WS_FRAG(sn + a_off[0] + A_PLANE);
-                        }
+                        al[NXT] = WS_FRAG(sn + a_off[0] + A_PLANE);
                     }
-                    if (j == JP && !(DML_WS_ABL & 2)) {     // the next step's poll, answered under the MFMAs
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) ACC(i, j) = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[i], ah[CUR], ACC(i, j), 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j == JP) {     // the next step's poll, answered under the MFMAs
 #pragma unroll
                         for (int w = 0; w < NLD; ++w) pl[w] = ws_ld(ready + w);
                     }
-                    if (j == JW && !(DML_WS_ABL & 2)) {
+                    if (j == JW) {
                         rflag = pl[0];
 #pragma unroll
                         for (int w = 1; w < NLD; ++w) rflag = min(rflag, pl[w]);
                         if (has_next) wait_ready(g + 2);
                     }
-                    if (j == JB && !(DML_WS_ABL & 1)) {
+                    if (MT >= 9) {                      // the next step's hi weight fragments, one per row group
+                        if (j >= JB && j < JB + NT) bn[j - JB] = WS_FRAG(sn + b_off[j - JB]);
+                    } else if (j == JB) {
 #pragma unroll
                         for (int i = 0; i < NT; ++i) bn[i] = WS_FRAG(sn + b_off[i]);
                     }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) ACC(i, j) = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[i], ah[(j + P) & 1], ACC(i, j), 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) ACC(i, j) = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[i], al[(j + P) & 1], ACC(i, j), 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) ACC(i, j) = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[i], ah[(j + P) & 1], ACC(i, j), 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#endif
                 }
-                if (!(DML_WS_ABL & 1)) {
 #pragma unroll
-                    for (int i = 0; i < NT; ++i) bl[i] = WS_FRAG(sn + b_off[i] + B_PLANE);
-                }
+                for (int i = 0; i < NT; ++i) bl[i] = WS_FRAG(sn + b_off[i] + B_PLANE);
                 __builtin_amdgcn_sched_barrier(0);
                 ++g;
             };
@@ -2380,14 +2175,14 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& a, const uint32_t x
         // forward, 144-row wave tiles: the BatchNorm statistics of the whole wave tile at once (ws_tile_stats)
         constexpr bool TILE_STATS = PL == 2 && MODE == 0 && MT == 9;
         if constexpr (TILE_STATS) {
-            if (a.stats != nullptr && !(DML_WS_ABL & 8)) ws_tile_stats<NT, MT / 3>(acc3, a, blk_m * BM + wm * (16 * MT), blk_n * BN + wn * 64, lr, lq);
+            if (a.stats != nullptr) ws_tile_stats<NT, MT / 3>(acc3, a, blk_m * BM + wm * (16 * MT), blk_n * BN + wn * 64, lr, lq);
         }
-        if constexpr (EPI != 0 && !(DML_WS_ABL & 8))
+        if constexpr (EPI != 0)
             conv_epilogue_rows_ops<NT, MT / 3, (EPI & 1) != 0, (EPI & 2) != 0>(
                 acc3, a, blk_m * BM + wm * (16 * MT), blk_n * BN + wn * 64, lane, rows_stage,
                 priv ? rows_stage : smem + ((g - 2) % NST) * SB + wave * (WS_STAT_ROWS * 256), smem + NST * SB + 64 + wave * MASK_STAGE);
 #pragma clang loop unroll(disable)
-        for (int h = 0; h < ((EPI != 0 || (DML_WS_ABL & 8)) ? 0 : MT / 3); ++h) {      // (ablation 8: no epilogue at all)
+        for (int h = 0; h < (EPI != 0 ? 0 : MT / 3); ++h) {
             const int mw0 = blk_m * BM + wm * (16 * MT) + h * WS_STAT_ROWS, nw0 = blk_n * BN + wn * 64;
             if constexpr (PL == 1) conv_epilogue<bf16_t, NT, 3, MODE, false>(acc3[0], a, mw0, nw0, lr, lq);
             else if (MODE == 0 && (a.bias != nullptr || a.post_scale != nullptr)) {
@@ -2425,15 +2220,34 @@ template <int MW, int NW, int MODE, int NLD, int PL = 1, int MT = WS_MT, int EPI
 __global__ __launch_bounds__((MW * NW + NLD) * 64) void conv_ws_kernel(const ConvArgs a, const uint32_t x_bytes, const uint32_t w_bytes) {
     conv_ws_body<MW, NW, MODE, NLD, PL, MT, EPI>(a, x_bytes, w_bytes);
 }
-// the half-tile configuration (144 x 128, two consumer + two loader waves): at most 256 registers, so that two workgroups share a CU
-template <int MODE, int EPI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_ws_half_kernel(const ConvArgs a, const uint32_t x_bytes,
-                                                                                                const uint32_t w_bytes) {
-    conv_ws_body<1, 2, MODE, 2, 2, WS_MT, EPI>(a, x_bytes, w_bytes);
+
+// The library's run-time switches, read once.  Tests select kernel families through them.
+//   DML_CONV_V1     set: bf16 launches on the register-staged kernel instead of the LDS-DMA ones
+//   DML_CONV_BM256  256-row tiles of the LDS-DMA kernel: 0 never, 1 the rule in launch_conv (default), 2 every eligible layer,
+//                   >= 64 the K threshold of the rule
+//   DML_CONV_WS     non-zero: bf16 launches on conv_ws_kernel wherever conv_ws_eligible allows (default 0)
+struct ConvSwitches {
+    bool v1;
+    int bm256, ws;
+};
+static const ConvSwitches& conv_switches() {
+    static const ConvSwitches s = {getenv("DML_CONV_V1") != nullptr, getenv("DML_CONV_BM256") ? atoi(getenv("DML_CONV_BM256")) : 1,
+                                   getenv("DML_CONV_WS") ? atoi(getenv("DML_CONV_WS")) : 0};
+    return s;
 }
 
-// may this launch run on conv_ws_kernel?  (shared by launch_conv and dml_conv_stat_rows)
-static bool conv_ws_eligible(const ConvArgs& a, const int64_t xb, const int64_t wb, const int mode = 1) {
+// bytes of the activation / weight operands with ES-byte elements (operand extents of the buffer descriptors)
+static int64_t conv_x_bytes(const ConvArgs& a, const int es) { return (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * es; }
+static int64_t conv_w_bytes(const ConvArgs& a, const int es) { return (int64_t)a.N * a.Ktot * es; }
+
+// bf16: may this launch run on the LDS-DMA kernels?  K tiles inside one tap, N > 32, tensors addressable with a 31-bit byte offset
+// (shared by launch_conv and dml_conv_stat_rows)
+static bool conv_dma_eligible(const ConvArgs& a, const int64_t xb, const int64_t wb) {
+    return !conv_switches().v1 && (a.C % BK) == 0 && a.R * a.S <= 32 && a.N > 32 && xb < (1ll << 31) && wb < (1ll << 31);
+}
+
+// ... and among them on conv_ws_kernel?  (shared by launch_conv and dml_conv_stat_rows)
+static bool conv_ws_eligible(const ConvArgs& a, const int64_t xb, const int64_t wb) {
     // bf16 plans: OPT-IN (DML_CONV_WS=1).  Per launch it wins where K is long (rule below), but in the train step the persistent
     // 150 KB-of-LDS workgroups keep the side stream's weight-gradient workgroups off the CUs they hold and static tile lists
     // cannot rebalance around them: whole step 391.5 / 392.2 images/s with it, 395.3 / 394.9 without (two interleaved pairs,
@@ -2441,8 +2255,7 @@ static bool conv_ws_eligible(const ConvArgs& a, const int64_t xb, const int64_t 
     // (forward-only for the long-K launches, where nothing runs beside the main stream, measured +0.1...0.4 % on the step -- and moved
     // the bf16 plan's rounding (48-row statistics groups) enough to redraw the chaotic 30-step trajectory of
     // tests/test_gpu_training_equivalence.py past its bar; not worth a different default)
-    static const int ws_on = getenv("DML_CONV_WS") ? atoi(getenv("DML_CONV_WS")) : 0;
-    if ((!ws_on && a.ws_min_tiles <= 0) || !a.w_tiled || (a.C % BK) != 0 || a.R * a.S > 32 || (a.N % 128) != 0) return false;
+    if ((!conv_switches().ws && a.ws_min_tiles <= 0) || !a.w_tiled || (a.C % BK) != 0 || a.R * a.S > 32 || (a.N % 128) != 0) return false;
     if (xb >= (1ll << 31) || wb >= (1ll << 31)) return false;
     // long K loops only: a consumer wave runs its tile's epilogue itself, with nothing of the same workgroup to cover it, and
     // below ~32 K steps per tile that costs more than the K loop gains (tools/bench_ws.py, profiles/r04_bench_ws_2.txt: K = 256
@@ -2457,8 +2270,7 @@ static bool conv_ws_eligible(const ConvArgs& a, const int64_t xb, const int64_t 
 // two planes, forward: 48 x 256 tiles instead of 144 x 256 for launches that leave most of the chip empty (launch_conv; also decides
 // the rows per statistics partial: dml_conv_stat_rows)
 static bool ws_planes_short(const ConvArgs& a, const int mode) {
-    static const int short_on = getenv("DML_WS_SHORT") ? atoi(getenv("DML_WS_SHORT")) : 1;
-    return mode == 0 && short_on != 0 && (a.N % 256) == 0 && ((a.M + 143) / 144) * (a.N / 256) * 2 <= 256;
+    return mode == 0 && (a.N % 256) == 0 && ((a.M + 143) / 144) * (a.N / 256) * 2 <= 256;
 }
 // rows of the GEMM per BatchNorm statistics partial of a two-plane FORWARD launch: the whole 144-row wave tile (ws_tile_stats) except on
 // the 48-row wave tiles (64 output channels, short tiles)
@@ -2482,8 +2294,7 @@ static bool conv_ws_planes_eligible(const ConvArgs& a, const int mode) {
           reinterpret_cast<uintptr_t>(a.post_scale) | reinterpret_cast<uintptr_t>(a.post_shift) |
           reinterpret_cast<uintptr_t>(a.post_mean)) & 15) != 0)
         return false;
-    const int64_t xb = (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2, wb = (int64_t)a.N * a.Ktot * 2;
-    return xb + a.x_plane_bytes < (1ll << 31) && wb + a.w_plane_bytes < (1ll << 31);
+    return conv_x_bytes(a, 2) + a.x_plane_bytes < (1ll << 31) && conv_w_bytes(a, 2) + a.w_plane_bytes < (1ll << 31);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3732,11 +3543,10 @@ static void fill_wgrad_args(WgradArgs& a, const DmlWgradDesc* d) {
 template <typename T, int MODE>
 int launch_conv(const ConvArgs& base, hipStream_t st) {
     ConvArgs a = base;
-    const int64_t xb64 = (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * (int64_t)sizeof(T);
-    const int64_t wb64 = (int64_t)a.N * a.Ktot * (int64_t)sizeof(T);
-    const bool small = xb64 < (1ll << 31) && wb64 < (1ll << 31);
-    a.x_bytes = small ? (uint32_t)xb64 : 0u;
-    a.w_bytes = small ? (uint32_t)wb64 : 0u;
+    const int64_t xb = conv_x_bytes(a, (int)sizeof(T)), wb = conv_w_bytes(a, (int)sizeof(T));
+    const bool small = xb < (1ll << 31) && wb < (1ll << 31);
+    a.x_bytes = small ? (uint32_t)xb : 0u;
+    a.w_bytes = small ? (uint32_t)wb : 0u;
     const bool aligned = (a.C % BK) == 0 && a.R * a.S <= 32 && small;
     a.nblk_m = (a.M + 127) / 128;
     // non-temporal epilogue stores for outputs that do not fit the L2 anyway (st16); smaller ones are better left there for
@@ -3756,15 +3566,12 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
         // runs; a 4-stage ring on the largest grids only: 360.2).  In isolation the two kernels are within +-5 % of each
         // other (tools/bench_conv.py); the register-staged kernel stays for fp32, unaligned channel counts (stem, final
         // conv) and N <= 32.
-        static const bool use_v1 = getenv("DML_CONV_V1") != nullptr;        // tuning / test switch: register-staged kernel
-        const int64_t xb = ((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx * 2 + (int64_t)a.C * 2;
-        const int64_t wb = (int64_t)a.N * a.Ktot * 2;
-        if (!use_v1 && aligned && a.N > 32 && xb < (1ll << 31) && wb < (1ll << 31)) {
+        if (conv_dma_eligible(a, xb, wb)) {
             // wave-specialised kernel (conv_ws_kernel): one persistent workgroup per CU on 144-row tiles, tile-major weights,
             // N a multiple of 128, enough tiles to fill the chip.  Same-box microbenchmarks against the ring kernel below
             // (profiles/r04_ws_probe_3.txt vs r04_ws_probe_1_shipped.txt): layer3 3x3 67.5 -> 43.6 us, 1x1 1024 -> 256
             // 37.6 -> 24.2, 1x1 256 -> 1024 38.4 -> 31.0, ASPP 3x3 385 -> 325-357, decoder 3x3 886 -> 825-870.
-            if (conv_ws_eligible(a, xb, wb, MODE)) {
+            if (conv_ws_eligible(a, xb, wb)) {
                 constexpr int CUS = 256, NLD = 3;
                 const bool wide = (a.N % 256) == 0;
                 const int bm = wide ? 144 : 288;
@@ -3813,7 +3620,7 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
             // In the plan (serial profile, r02 v3 -> v5): ASPP forward 1.14 -> 0.98 ms, ASPP data gradients 1.12 -> 1.01,
             // decoder forward 0.95 -> 0.86, layer4 3x3 -0.05; but layer3's 3x3 (K = 2304, only 288 tiles of 256 rows) LOSES
             // 0.24 ms over its 44 launches -- one 72-step tile per CU at two waves per SIMD -- hence the tile-count clause.
-            static const int bm256 = getenv("DML_CONV_BM256") ? atoi(getenv("DML_CONV_BM256")) : 1;
+            const int bm256 = conv_switches().bm256;
             const int tiles256 = ((a.M + 255) / 256) * (a.N / 128);
             const bool long_k = bm256 >= 64 ? a.Ktot >= bm256 : (a.Ktot >= 4608 || (a.Ktot >= 2304 && tiles256 >= 512));
             // The 256-row tile runs as 4 waves on 128 x 64 WAVE tiles (conv_igemm_dma_kernel<..., 256, 128>: 32 MFMAs per wave and
@@ -3865,7 +3672,7 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
     if constexpr (sizeof(T) == 4 && MODE != 2) {
         if (conv_ws_planes_eligible(a, MODE)) {
             // fp32 tensors, products of two fp16 planes per operand on the matrix cores (DmlConvDesc.x_planes ...)
-            constexpr int CUS = 256, NLD = DML_WS_PLANES_NLD;
+            constexpr int CUS = 256, NLD = WS_PLANES_NLD;
             const bool wide = (a.N % 256) == 0;
             // 64 output channels (layer1's 3x3, the 256 -> 64 1x1, the data gradients of the 64 -> 256 1x1): 192 x 64 tiles on four
             // 48 x 64 wave tiles.  On the 288 x 128 configuration half of every tile -- MFMAs and DMA pieces -- was empty
@@ -3881,26 +3688,10 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
             a.nblk_n = wide ? a.N / 256 : (n64 ? 1 : (a.N + 127) / 128);      // (a last 128-wide block may be half empty: zero rows, no stores)
             const int ntiles = a.nblk_m * a.nblk_n;
             const int grid = ntiles < CUS ? ntiles : CUS;
-            const uint32_t xpb = (uint32_t)((((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2), wpb = (uint32_t)((int64_t)a.N * a.Ktot * 2);
-            // Half-tile configuration (round 6): short K loops with several tiles per workgroup -- the layer3 1x1
-            // launches whose K loops (HBM nearly idle) and epilogues (matrix cores idle) alternate.  144 x 128 tiles, two consumer
-            // and two loader waves, 74 KB of LDS: TWO workgroups per CU, one's epilogue under the other's K loop.
-            static const int half_on = getenv("DML_WS_HALF") ? atoi(getenv("DML_WS_HALF")) : 0;
-            static const int half_kt = getenv("DML_WS_HALF_KT") ? atoi(getenv("DML_WS_HALF_KT")) : 32;
-            static const int half_stag = getenv("DML_WS_HALF_STAGGER") ? atoi(getenv("DML_WS_HALF_STAGGER")) : 0;
-            const int half_tiles = ((a.M + 143) / 144) * (a.N / 128);
-            const bool half = half_on != 0 && !n64 && (a.N % 128) == 0 && a.Ktot / BK <= half_kt && a.Ktot / BK >= 2 &&
-                              half_tiles >= (half_on == 2 ? 1 : 4) * CUS;
-            if (half) {
-                a.nblk_m = (a.M + 143) / 144;
-                a.nblk_n = a.N / 128;
-                a.half_stagger = half_stag;
-            }
+            const uint32_t xpb = (uint32_t)conv_x_bytes(a, 2), wpb = (uint32_t)conv_w_bytes(a, 2);
             auto go = [&](auto epi_c) {
                 constexpr int EPI = decltype(epi_c)::value;
-                if (half)
-                    hipLaunchKernelGGL((conv_ws_half_kernel<MODE, EPI>), dim3(half_tiles < 2 * CUS ? half_tiles : 2 * CUS), dim3(256), 0, st, a, xpb, wpb);
-                else if (shortm) {
+                if (shortm) {
                     if constexpr (MODE == 0 && EPI == 0)
                         hipLaunchKernelGGL((conv_ws_kernel<1, 4, 0, NLD, 2, 3, 0>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, xpb, wpb);
                 } else if (n64)
@@ -3911,9 +3702,8 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
                     hipLaunchKernelGGL((conv_ws_kernel<2, 2, MODE, NLD, 2, WS_MT, EPI>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, xpb, wpb);
             };
             // data gradients: one instantiation per set of epilogue operands (conv_epilogue_rows_ops)
-            const int epi = (MODE == 1 && DML_WS_EPI_OPS != 0)
-                                ? ((a.accum != 0 || a.res_dz != nullptr) ? 1 : 0) | (a.bnr_partials != nullptr ? 2 : 0) : 0;
-            if constexpr (MODE == 1 && DML_WS_EPI_OPS != 0) {
+            const int epi = MODE == 1 ? ((a.accum != 0 || a.res_dz != nullptr) ? 1 : 0) | (a.bnr_partials != nullptr ? 2 : 0) : 0;
+            if constexpr (MODE == 1) {
                 if (epi == 3) go(std::integral_constant<int, 3>{});
                 else if (epi == 2) go(std::integral_constant<int, 2>{});
                 else if (epi == 1) go(std::integral_constant<int, 1>{});
@@ -3964,6 +3754,48 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
     }
 }
 
+// The launch a descriptor describes, before launch_conv picks its kernel: every field of the descriptor that is in effect, the rest
+// zero.  Shared by dml_conv_igemm, which validates the descriptor first, and dml_conv_stat_rows, so that both see the same arguments.
+static ConvArgs conv_args(const DmlConvDesc* d) {
+    ConvArgs a{};
+    a.x = d->x; a.w = d->w; a.y = d->y; a.bias = d->bias; a.stats = d->stats;
+    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
+    a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
+    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad; a.pad_x = d->pad_w_set ? d->pad_w : d->pad;
+    a.M = d->B * d->Ho * d->Wo;
+    a.Ktot = d->R * d->S * d->C;
+    a.y_f32 = d->y_f32; a.accum = d->accum;
+    a.div_wo = make_fastdiv((uint32_t)d->Wo);
+    a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
+    a.div_c = make_fastdiv((uint32_t)d->C);
+    a.w_tiled = d->w_tiled ? 1 : 0;
+    a.ws_min_tiles = d->ws_min_tiles;
+    a.f32_split = d->dtype == DML_F32 ? d->f32_split : 0;
+    if (a.f32_split == 2 && d->x_planes && d->w_planes) {
+        a.x_planes = d->x_planes; a.w_planes = d->w_planes; a.x_unscale = d->x_unscale; a.w_unscale = d->w_unscale;
+        a.x_plane_bytes = (uint32_t)(d->x_plane_stride * 2); a.w_plane_bytes = (uint32_t)(d->w_plane_stride * 2);
+    }
+    if (d->acc32) { a.acc32 = d->acc32; a.acc32_ld = d->acc32_ld; }
+    if (d->res_dz) { a.res_dz = d->res_dz; a.res_mask = d->res_mask; a.res_ld = d->res_ld; }
+    a.tail_q = 1;
+    if (d->tail_ws && d->tail_counters && d->tail_ws_elems > 0 && d->tail_counters_len > 0) {
+        a.tail_ws = d->tail_ws; a.tail_cnt = d->tail_counters;
+        a.tail_ws_elems_ = d->tail_ws_elems; a.tail_cnt_len_ = d->tail_counters_len;
+    }
+    if (d->post_scale) {
+        a.post_scale = d->post_scale; a.post_shift = d->post_shift; a.post_mean = d->post_mean; a.post_res = d->post_res;
+        a.post_ldres = d->post_ldres; a.post_relu = d->post_relu;
+    }
+    if (d->bnr_partials) {
+        a.bnr_y = d->bnr_y; a.bnr_mask = d->bnr_mask; a.bnr_mean = d->bnr_mean; a.bnr_invstd = d->bnr_invstd;
+        a.bnr_partials = d->bnr_partials; a.bnr_ldy = d->bnr_ldy; a.bnr_relu = d->bnr_relu;
+        if (d->dtype == DML_F32) a.bnr_gmax = d->bnr_gmax;
+        a.bnr_inc = d->bnr_inc != 0 ? 1 : 0;
+    }
+    if (d->sub_grid) { a.sub_grid = 1; a.sub_y = d->sub_y; a.sub_x = d->sub_x; }
+    return a;
+}
+
 }  // namespace
 
 // Rows of the GEMM covered by one statistics partial (DmlConvDesc.stats / bnr_partials) of THIS launch: 48 where the
@@ -3971,26 +3803,13 @@ int launch_conv(const ConvArgs& base, hipStream_t st) {
 // dml_bn_finalize_rows / dml_bn_moments_rows (the BN-backward finalize only needs the group count).
 extern "C" int dml_conv_stat_rows(const DmlConvDesc* d) {
     if (!d) return DML_STAT_ROWS;
-    ConvArgs a;
-    a.w_tiled = d->w_tiled; a.C = d->C; a.R = d->R; a.S = d->S; a.N = d->N; a.ws_min_tiles = d->ws_min_tiles;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.ldx = d->ldx;
-    a.M = d->B * d->Ho * d->Wo;
-    a.Ktot = d->R * d->S * d->C;
-    a.y = d->y; a.ldy = d->ldy; a.bias = d->bias; a.accum = d->accum;
-    a.post_scale = d->post_scale; a.post_shift = d->post_shift; a.post_mean = d->post_mean; a.post_res = d->post_res;
-    a.post_ldres = d->post_ldres;
-    if (d->dtype == DML_F32) {
-        a.f32_split = d->f32_split; a.x_planes = d->x_planes; a.w_planes = d->w_planes;
-        a.x_unscale = d->x_unscale; a.w_unscale = d->w_unscale;
-        a.x_plane_bytes = (uint32_t)(d->x_plane_stride * 2); a.w_plane_bytes = (uint32_t)(d->w_plane_stride * 2);
+    const ConvArgs a = conv_args(d);
+    if (d->dtype == DML_F32)      // (plane strides dml_conv_igemm accepts: a larger one would wrap in x_plane_bytes)
         return (d->x_plane_stride < (1ll << 30) && d->w_plane_stride < (1ll << 30) && conv_ws_planes_eligible(a, d->mode))
                    ? ws_planes_stat_rows(a, d->mode) : DML_STAT_ROWS;
-    }
-    if (d->dtype != DML_BF16 || !d->w_tiled) return DML_STAT_ROWS;
-    const int64_t xb = ((int64_t)(d->B * d->Hi) * d->Wi - 1) * d->ldx * 2 + (int64_t)d->C * 2;
-    const int64_t wb = (int64_t)d->N * d->R * d->S * d->C * 2;
-    static const bool use_v1 = getenv("DML_CONV_V1") != nullptr;
-    return (!use_v1 && conv_ws_eligible(a, xb, wb, d->mode)) ? WS_STAT_ROWS : DML_STAT_ROWS;
+    if (d->dtype != DML_BF16) return DML_STAT_ROWS;
+    const int64_t xb = conv_x_bytes(a, 2), wb = conv_w_bytes(a, 2);
+    return (conv_dma_eligible(a, xb, wb) && conv_ws_eligible(a, xb, wb)) ? WS_STAT_ROWS : DML_STAT_ROWS;
 }
 
 extern "C" int dml_conv_igemm(const DmlConvDesc* d, void* stream) {
@@ -4003,41 +3822,23 @@ extern "C" int dml_conv_igemm(const DmlConvDesc* d, void* stream) {
     if (d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->N <= 0 || d->R <= 0 || d->S <= 0) return DML_EINVAL;
     if ((int64_t)d->B * d->Ho * d->Wo >= (1ll << 31)) return DML_EINVAL;
     if (d->stats && d->bias) return DML_EINVAL;
-    ConvArgs a;
-    a.x = d->x; a.w = d->w; a.y = d->y; a.bias = d->bias; a.stats = d->stats; a.dbg = nullptr;
-    a.bnr_y = nullptr; a.bnr_mask = nullptr; a.bnr_mean = nullptr; a.bnr_invstd = nullptr; a.bnr_partials = nullptr;
-    a.bnr_gmax = nullptr;
-    a.bnr_ldy = 0; a.bnr_relu = 0;
-    a.post_scale = nullptr; a.post_shift = nullptr; a.post_mean = nullptr; a.post_res = nullptr; a.post_ldres = 0;
-    a.post_relu = 0;
-    a.tail_ws = nullptr; a.tail_cnt = nullptr; a.tail_full = 0; a.tail_q = 1; a.tail_ws_elems_ = 0; a.tail_cnt_len_ = 0;
-    a.res_dz = nullptr; a.res_mask = nullptr; a.res_ld = 0; a.nt_out = 0; a.half_stagger = 0;
-    a.acc32 = nullptr; a.acc32_ld = 0; a.f32_split = d->dtype == DML_F32 ? d->f32_split : 0;
+    const ConvArgs a = conv_args(d);
     if (a.f32_split < 0 || a.f32_split > 2) return DML_EINVAL;
-    a.x_planes = nullptr; a.w_planes = nullptr; a.x_unscale = nullptr; a.w_unscale = nullptr; a.x_plane_bytes = a.w_plane_bytes = 0;
-    if (a.f32_split == 2 && d->x_planes && d->w_planes) {
+    if (a.x_planes) {
         if (!d->x_unscale || !d->w_unscale || d->x_plane_stride <= 0 || d->w_plane_stride <= 0 ||
             d->x_plane_stride >= (1ll << 30) || d->w_plane_stride >= (1ll << 30))
             return DML_EINVAL;
         if ((reinterpret_cast<uintptr_t>(d->x_planes) & 15) || (reinterpret_cast<uintptr_t>(d->w_planes) & 15) ||
             (d->x_plane_stride & 7) || (d->w_plane_stride & 7))
             return DML_EALIGN;
-        a.x_planes = d->x_planes; a.w_planes = d->w_planes; a.x_unscale = d->x_unscale; a.w_unscale = d->w_unscale;
-        a.x_plane_bytes = (uint32_t)(d->x_plane_stride * 2); a.w_plane_bytes = (uint32_t)(d->w_plane_stride * 2);
     }
-    a.w_tiled = 0;
-    a.ws_min_tiles = d->ws_min_tiles;
-    if (d->w_tiled) {
-        if (d->dtype != DML_BF16 || d->C % BK || d->N % 64) return DML_EUNSUPPORTED;
-        a.w_tiled = 1;
-    }
+    if (d->w_tiled && (d->dtype != DML_BF16 || d->C % BK || d->N % 64)) return DML_EUNSUPPORTED;
     if (d->acc32) {
         // fp32 staging of a gradient with several producers: the 16-byte-vector bf16 path of the data gradient only
         if (d->mode != 1 || d->dtype != DML_BF16 || d->y_f32 || d->accum || d->res_dz || d->bnr_partials) return DML_EINVAL;
         if (d->N % 8 || d->ldy % 8 || d->acc32_ld % 4 || (reinterpret_cast<uintptr_t>(d->y) & 15) ||
             (reinterpret_cast<uintptr_t>(d->acc32) & 15) || d->N <= 32)
             return DML_EALIGN;
-        a.acc32 = d->acc32; a.acc32_ld = d->acc32_ld;
     }
     if (d->res_dz) {
         // masked residual gradient in the epilogue: the 16-byte-vector bf16 path of the data gradient only
@@ -4051,21 +3852,12 @@ extern "C" int dml_conv_igemm(const DmlConvDesc* d, void* stream) {
         } else if (d->N % 64 || d->res_ld % 4 || ((reinterpret_cast<uintptr_t>(d->res_dz) | reinterpret_cast<uintptr_t>(d->res_mask)) & 15)) {
             return DML_EALIGN;      // (16 mask bytes per pixel row and 64 channels are one load)
         }
-        a.res_dz = d->res_dz; a.res_mask = d->res_mask; a.res_ld = d->res_ld;
     }
-    if (d->tail_ws && d->tail_counters && d->tail_ws_elems > 0 && d->tail_counters_len > 0) {
-        if (reinterpret_cast<uintptr_t>(d->tail_ws) & 15) return DML_EALIGN;
-        a.tail_ws = d->tail_ws; a.tail_cnt = d->tail_counters;
-        a.tail_ws_elems_ = d->tail_ws_elems; a.tail_cnt_len_ = d->tail_counters_len;
-    }
+    if (a.tail_ws && (reinterpret_cast<uintptr_t>(a.tail_ws) & 15)) return DML_EALIGN;
     if (d->post_scale) {
         if (d->mode != 0 || !d->post_shift || !d->post_mean || d->stats || d->bias || d->accum || d->y_f32) return DML_EINVAL;
         if (d->post_res && (d->post_ldres % vec || (reinterpret_cast<uintptr_t>(d->post_res) & 15))) return DML_EALIGN;
-        a.post_scale = d->post_scale; a.post_shift = d->post_shift; a.post_mean = d->post_mean; a.post_res = d->post_res;
-        a.post_ldres = d->post_ldres; a.post_relu = d->post_relu;
     }
-    a.bnr_gmax = nullptr;
-    bool bnr_inc_req = false;
     if (d->bnr_partials) {
         // fused BN-backward reduce: data-gradient mode; bf16 result stored as 16-byte vectors, 8-channel mask bytes -- or fp32 on the
         // two-plane kernel (checked below, once the launch is described), 4-channel mask bytes
@@ -4082,37 +3874,17 @@ extern "C" int dml_conv_igemm(const DmlConvDesc* d, void* stream) {
                   reinterpret_cast<uintptr_t>(d->bnr_mean) | reinterpret_cast<uintptr_t>(d->bnr_invstd) |
                   (d->bnr_relu ? reinterpret_cast<uintptr_t>(d->bnr_mask) : 0)) & 15) != 0)
                 return DML_EALIGN;
-            a.bnr_gmax = d->bnr_gmax;
         }
-        a.bnr_y = d->bnr_y; a.bnr_mask = d->bnr_mask; a.bnr_mean = d->bnr_mean; a.bnr_invstd = d->bnr_invstd;
-        a.bnr_partials = d->bnr_partials; a.bnr_ldy = d->bnr_ldy; a.bnr_relu = d->bnr_relu;
-        bnr_inc_req = d->bnr_inc != 0;
     }
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
-    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad; a.pad_x = d->pad; a.sub_grid = 0; a.sub_y = a.sub_x = 0; a.bnr_inc = 0;
-    a.M = d->B * d->Ho * d->Wo;
-    a.Ktot = d->R * d->S * d->C;
-    a.y_f32 = d->y_f32; a.accum = d->accum;
-    a.bnr_inc = 0;
-    if (bnr_inc_req) {
-        // (only the two-plane row epilogue with both operand sets knows the increment: an accumulating fp32 launch)
-        if (!d->accum || d->dtype != DML_F32 || d->res_dz) return DML_EUNSUPPORTED;
-        a.bnr_inc = 1;
-    }
-    if (d->pad_w_set) a.pad_x = d->pad_w;
+    // (only the two-plane row epilogue with both operand sets knows the increment: an accumulating fp32 launch)
+    if (a.bnr_inc && (!d->accum || d->dtype != DML_F32 || d->res_dz)) return DML_EUNSUPPORTED;
     if (d->sub_grid) {
         // a parity class of a stride-2 data gradient: stride-1 geometry on dY's grid, the two-plane kernel's row epilogues only
         if (d->mode != 1 || d->stride != 1 || d->dil != 1 || d->Hi != d->Ho || d->Wi != d->Wo || (unsigned)d->sub_y > 1u ||
             (unsigned)d->sub_x > 1u || d->dtype != DML_F32)
             return DML_EINVAL;
         if ((int64_t)4 * d->B * d->Ho * d->Wo * (int64_t)d->ldy * 4 >= (1ll << 31)) return DML_EUNSUPPORTED;
-        a.sub_grid = 1; a.sub_y = d->sub_y; a.sub_x = d->sub_x;
     }
-    a.nblk_n = a.nblk_m = 0;
-    a.div_wo = make_fastdiv((uint32_t)d->Wo);
-    a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
-    a.div_c = make_fastdiv((uint32_t)d->C);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((a.sub_grid || a.pad_x != a.pad) && (d->dtype == DML_BF16 || a.acc32)) return DML_EUNSUPPORTED;
     if (a.acc32) return launch_conv<bf16_t, 2>(a, st);
@@ -4125,52 +3897,6 @@ extern "C" int dml_conv_igemm(const DmlConvDesc* d, void* stream) {
     if (d->f32_split == 2 && d->x_planes && d->x == d->x_planes && !conv_ws_planes_eligible(a, d->mode)) return DML_EUNSUPPORTED;
     return d->mode == 0 ? launch_conv<float, 0>(a, st) : launch_conv<float, 1>(a, st);
 }
-
-// tuning builds only (make tuning -> libdmlnet_hip_tuning.so; tools/bench_conv.py abl / phases / dmaphases): the 128 x 128
-// forward kernels with parts removed or with s_memtime stamps.  Not part of the ABI, not in the product library.
-#ifdef DML_TUNING
-extern "C" int dml_debug_conv_ablate(const DmlConvDesc* d, int abl, float* dbg, const float* aux0, const float* aux1, void* stream) {
-    ConvArgs a;
-    a.x = d->x; a.w = d->w; a.y = d->y; a.bias = nullptr; a.stats = d->stats;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
-    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad; a.pad_x = d->pad; a.sub_grid = 0; a.sub_y = a.sub_x = 0; a.bnr_inc = 0;
-    a.M = d->B * d->Ho * d->Wo; a.Ktot = d->R * d->S * d->C; a.y_f32 = 0; a.accum = 0;
-    a.nblk_m = (a.M + 127) / 128; a.nblk_n = (a.N + 127) / 128;
-    a.div_wo = make_fastdiv((uint32_t)d->Wo); a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
-    a.div_c = make_fastdiv((uint32_t)d->C);
-    a.dbg = dbg;
-    a.bnr_y = nullptr; a.bnr_mask = nullptr; a.bnr_mean = nullptr; a.bnr_invstd = nullptr; a.bnr_partials = nullptr;
-    a.bnr_gmax = nullptr;
-    a.bnr_ldy = 0; a.bnr_relu = 0;
-    a.post_scale = nullptr; a.post_shift = nullptr; a.post_mean = nullptr; a.post_res = nullptr; a.post_ldres = 0;
-    a.post_relu = 0;
-    a.tail_ws = nullptr; a.tail_cnt = nullptr; a.tail_full = 0; a.tail_q = 1; a.tail_ws_elems_ = 0; a.tail_cnt_len_ = 0;
-    a.res_dz = nullptr; a.res_mask = nullptr; a.res_ld = 0; a.nt_out = 0; a.half_stagger = 0; a.acc32 = nullptr; a.acc32_ld = 0; a.f32_split = 0;
-    a.w_tiled = 0; a.ws_min_tiles = 0;
-    a.x_planes = nullptr; a.w_planes = nullptr; a.x_unscale = nullptr; a.w_unscale = nullptr; a.x_plane_bytes = a.w_plane_bytes = 0;
-    a.x_bytes = (uint32_t)((((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2);
-    a.w_bytes = (uint32_t)((int64_t)a.N * a.Ktot * 2);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    dim3 grid(a.nblk_m * a.nblk_n);
-    if (abl == 0) hipLaunchKernelGGL((conv_igemm_kernel<bf16_t, 128, true, 0, 0>), grid, dim3(NTHREADS), 0, st, a);
-    else if (abl == 1) hipLaunchKernelGGL((conv_igemm_kernel<bf16_t, 128, true, 0, 1>), grid, dim3(NTHREADS), 0, st, a);
-    else if (abl == 3) hipLaunchKernelGGL((conv_igemm_kernel<bf16_t, 128, true, 0, 3>), grid, dim3(NTHREADS), 0, st, a);
-    else if (abl == 5) {          // the LDS-DMA 128 x 128 kernel with phase stamps; dbg = 8 floats per wave
-        hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 0, 3, 3, 128, 64, true>), grid, dim3(NTHREADS), 0, st, a, a.x_bytes, a.w_bytes);
-    }
-    else if (abl == 4) {
-        a.dbg = nullptr;
-        a.bnr_mean = aux0; a.bnr_invstd = aux1;       // per INPUT channel: the probe's scale / shift
-        if (!a.bnr_mean || !a.bnr_invstd) return DML_EINVAL;
-        hipLaunchKernelGGL((conv_igemm_kernel<bf16_t, 128, true, 0, 4>), grid, dim3(NTHREADS), 0, st, a);
-    }
-    else hipLaunchKernelGGL((conv_igemm_kernel<bf16_t, 128, true, 0, 2>), grid, dim3(NTHREADS), 0, st, a);
-    DML_LAUNCH_CHECK();
-    return 0;
-}
-
-#endif
 
 extern "C" int dml_conv_wgrad(const DmlWgradDesc* d, void* stream) {
     if (!d || !d->x || !d->dy || !d->dw) return DML_EINVAL;
@@ -4329,7 +4055,7 @@ extern "C" int dml_conv_wgrad(const DmlWgradDesc* d, void* stream) {
         const int64_t nrs = (int64_t)a.N * a.R * a.S;
         // (one-wave blocks: they start beside the persistent data-gradient workgroups of the other stream instead of waiting for one
         // to retire -- 28.6 us per launch in the overlapped trace against 9.8 alone, 122 launches per step; see dml_bn_bwd_apply)
-        static const int rt = getenv("DML_WGRAD_REDUCE_THREADS") ? atoi(getenv("DML_WGRAD_REDUCE_THREADS")) : 64;
+        constexpr int rt = 64;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(nrs * cm, rt, 256 * 8 * (256 / rt)), 1), dim3(rt), 0, st, d->ws, d->dw, sk, nrs,
                            cm, d->C, 1, 0);
         DML_LAUNCH_CHECK();

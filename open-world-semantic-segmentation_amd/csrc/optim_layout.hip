@@ -280,6 +280,7 @@ extern "C" int dml_prep_weights(const DmlPrepDesc* descs_device, int count, int 
 // narrow exponent range is met by scaling the whole tensor with a power of two that puts its largest magnitude just below 2^15
 // (products up to 2^30 accumulate in fp32; small elements lose relative precision only below 2^-29 of the maximum).
 // ------------------------------------------------------------------------------------------------
+namespace {
 constexpr int H2_MAXBLK = 1024;
 __global__ __launch_bounds__(256) void h2_amax_kernel(const float* __restrict__ x, int64_t rows, int C, int ld, float* __restrict__ work) {
     // per-workgroup maxima of |x| (as unsigned bit patterns: order-preserving for non-negative floats, NaN ends up largest)
@@ -349,6 +350,7 @@ __global__ __launch_bounds__(256) void h2_split_kernel(const float* __restrict__
         *reinterpret_cast<h8*>(planes + plane_stride + off) = lo;
     }
 }
+}  // namespace
 
 extern "C" int dml_h2_split(const float* x, int64_t rows, int32_t C, int32_t ld, void* planes, int64_t plane_stride, int32_t ldp,
                             int32_t layout, float* work, int32_t amax_known, void* stream) {
@@ -372,6 +374,7 @@ extern "C" int dml_h2_split(const float* x, int64_t rows, int32_t C, int32_t ld,
 
 // the same for a table of tensors in two launches (every weight copy of a plan after each optimizer step: ~200 tensors, whose
 // ~400 tiny launches cost ~2 ms of the step on the main stream)
+namespace {
 constexpr int H2_TABLE_BLK = 64;           // workgroups per tensor
 __global__ __launch_bounds__(256) void h2_amax_table_kernel(const DmlH2Desc* __restrict__ table) {
     const DmlH2Desc d = table[blockIdx.y];
@@ -421,6 +424,7 @@ __global__ __launch_bounds__(256) void h2_split_table_kernel(const DmlH2Desc* __
         *reinterpret_cast<h8*>(planes + d.plane_stride + off) = lo;
     }
 }
+}  // namespace
 
 extern "C" int dml_h2_split_table(const DmlH2Desc* table_device, int count, void* stream) {
     if (!table_device || count <= 0) return DML_EINVAL;

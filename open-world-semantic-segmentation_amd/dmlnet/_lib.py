@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DML_LIB_PATH: another build of the same library (A/B runs of two builds, the tuning build `make tuning`) -- selected here, not by
+# DML_LIB_PATH: another build of the same library (A/B runs of two builds) -- selected here, not by
 # copying over the in-tree file another process may have mapped
 LIB_PATH = os.environ.get("DML_LIB_PATH") or os.path.join(_HERE, "libdmlnet_hip.so")
 
