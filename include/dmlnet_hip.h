@@ -575,6 +575,41 @@ int dml_pil_resize_normalize(const uint8_t* img, int h, int w, const DmlResizeSc
 int dml_segm_to_label(const uint8_t* segm, int64_t n, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scale / resize / pad / crop stage of the input pipeline (utils/ext_transforms.py:68-146, 328-428 of the
+ * reference: ExtRandomScale, ExtScale, ExtResize, ExtCenterCrop, ExtRandomCrop with padding / pad_if_needed), on
+ * a batch of uint8 NHWC frames of one size, a different scale per sample, one launch.  Per sample the kernel sees
+ * a VIRTUAL image -- the frame resized to (Hs, Ws) -- and a th x tw output window whose origin in that image may
+ * be negative and whose extent may pass its far edge; a pixel outside the virtual image is 0, in the image and in
+ * the label (F.pad's default fill; Image.crop beyond the image).  Image: the 8-bit BILINEAR resampler described
+ * above, restricted to the window.  Label: Pillow's NEAREST resize (Geometry.c, ImagingScaleAffine: the source
+ * index is int(xo) of a double that starts at 0.5 * in / out and grows by in / out per output pixel), as a gather
+ * through host-built index tables.  The window feeds dml_aug_contrast_sum / dml_aug_apply(_encoded) with
+ * i = j = 0 and frame size (th, tw).
+ * All tables of a batch live in ONE device int32 buffer `tables` (table_len elements); a sample names its own by
+ * element offsets.  A window column / row outside the virtual image has tap count 0 (and label index -1); an axis
+ * whose size does not change carries the identity (one tap of weight 2^22), which the arithmetic passes through
+ * unchanged.  Rows above the virtual image carry the first inside row's first source row, rows below it the last
+ * inside row's end, so that a band's source rows are [vbounds[first][0], vbounds[last][0] + vbounds[last][1]).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct DmlScaleWindow {
+    int32_t hbounds;   /* [tw][2] (first source column, tap count) of each window column                   */
+    int32_t hcoef;     /* [tw][kh] fixed-point weights (22 fraction bits)                                  */
+    int32_t vbounds;   /* [th][2] (first source row, tap count) of each window row                         */
+    int32_t vcoef;     /* [th][kv]                                                                          */
+    int32_t lrow;      /* [th] source row of the label's window row, -1 outside                            */
+    int32_t lcol;      /* [tw] source column of the label's window column, -1 outside                      */
+    int32_t kh, kv;    /* widths of hcoef / vcoef                                                           */
+} DmlScaleWindow;
+/* img [B,H,W,3], lbl [B,H,W] (optional, with out_lbl) -> out_img [B,th,tw,3], out_lbl [B,th,tw], all uint8.
+ * `samples`: DEVICE array of B.  band_rows: window rows per workgroup (a band of 64 columns); lds_rows: upper
+ * bound of the source rows any band of any sample reads (<= 256, else DML_EUNSUPPORTED).  The caller validates
+ * the tables against the frame before the upload; the kernel clamps every index it reads from them all the same
+ * (an out-of-frame entry contributes nothing). */
+int dml_aug_scale_window(const uint8_t* img, const uint8_t* lbl, const DmlScaleWindow* samples,
+                         const int32_t* tables, int64_t table_len, uint8_t* out_img, uint8_t* out_lbl, int B,
+                         int H, int W, int th, int tw, int band_rows, int lds_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pyramid-pooling decoder of the anomaly model (anomaly/models/models.py:586-687,
  * eval_ood_traditional.py:198-210 of the reference), inference only.
  * ---------------------------------------------------------------------------------------------- */

@@ -15,9 +15,13 @@ struct Px { uint32_t r, g, b; };
 __device__ __forceinline__ uint32_t luma(const Px p) { return (p.r * 19595u + p.g * 38470u + p.b * 7471u + 0x8000u) >> 16; }
 
 // Image.blend: float32 a + f*(b - a), multiply and add rounded separately (no contraction), truncation to uint8;
-// clipped first when f is outside [0, 1]
+// clipped first when f is outside [0, 1].  Plain operators under the pragma: __fmul_rn / __fadd_rn are inline functions of plain
+// operators that the compiler fuses under its default contraction (fused, 105 + 0.8f * (0 - 105) is 20.999998 -> 20 where
+// Pillow has 21: rare on image content, systematic on the constant zero border of a padded crop).
 __device__ __forceinline__ uint32_t blend1(uint32_t a, uint32_t b, float f, bool interp) {
-    const float t = __fadd_rn((float)a, __fmul_rn(f, __fsub_rn((float)b, (float)a)));
+#pragma clang fp contract(off)
+    const float p = f * ((float)b - (float)a);
+    const float t = (float)a + p;
     if (interp) return (uint32_t)t;
     return t <= 0.f ? 0u : (t >= 255.f ? 255u : (uint32_t)t);
 }

@@ -107,6 +107,13 @@ class ResizeScale(C.Structure):
 
 RESIZE_MAX_SCALES = 8
 
+
+class ScaleWindow(C.Structure):
+    """DmlScaleWindow: one sample of a dml_aug_scale_window launch (element offsets into the batch's table buffer)"""
+    _fields_ = [("hbounds", C.c_int32), ("hcoef", C.c_int32), ("vbounds", C.c_int32), ("vcoef", C.c_int32),
+                ("lrow", C.c_int32), ("lcol", C.c_int32), ("kh", C.c_int32), ("kv", C.c_int32)]
+
+
 _PROTOS = {
     "dml_abi_version": (c_i, []),
     "dml_target_arch": (C.c_char_p, []),
@@ -182,6 +189,7 @@ _PROTOS = {
     "dml_label_encode": (c_i, [c_p, C.c_int64, c_p, c_p, c_p, c_p, c_p]),
     "dml_pil_resize_normalize": (c_i, [c_p, c_i, c_i, C.POINTER(ResizeScale), c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
     "dml_segm_to_label": (c_i, [c_p, c_i64, c_p, c_p]),
+    "dml_aug_scale_window": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_adaptive_avgpool_ws_elems": (c_i64, [c_i, c_i, c_i, c_i, c_i]),
     "dml_adaptive_avgpool_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_proto_dist_nhwc": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),

@@ -44,6 +44,9 @@ def get_argparser():
     p.add_argument("--val_images", type=int, default=2, help="synthetic frames scored at every --val_interval")
     p.add_argument("--frame_height", type=int, default=1024, help="synthetic source frames (Cityscapes: 1024 x 2048)")
     p.add_argument("--frame_width", type=int, default=2048)
+    p.add_argument("--scale_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="scale-augmented train transform of the reference's get_dataset: ExtRandomScale((LO, HI)) then "
+                        "ExtRandomCrop(crop_size, pad_if_needed=True) (default: crop only)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f16x2", "f32x3"],
                    help="bf16: bf16 storage (throughput mode); f32: exact fp32 MFMA (the reference's arithmetic); f16x2 / f32x3: fp32 tensors with the convolution products on the fp16 / bf16 matrix cores (fp32-accurate splits, bench.py's headline is f16x2)")
     # the rest of the reference's surface (main_embedding.py:27-99 there): accepted so that its command lines keep
@@ -142,8 +145,12 @@ def main():
     frame_labels[:, : max(1, fh * 38 // 768)] = 0 if raw_ids else 255              # raw id 0 = 'unlabeled' -> 255
     frame_labels = frame_labels.to(device)
     luts = Cityscapes.label_luts(unknown) if raw_ids else None
-    train_transform = et.ExtCompose([
-        et.ExtRandomCrop(size=(opts.crop_size, opts.crop_size)),
+    if opts.scale_range is not None:                                               # main.py get_dataset of the reference
+        head = [et.ExtRandomScale((opts.scale_range[0], opts.scale_range[1])),
+                et.ExtRandomCrop(size=(opts.crop_size, opts.crop_size), pad_if_needed=True)]
+    else:
+        head = [et.ExtRandomCrop(size=(opts.crop_size, opts.crop_size))]
+    train_transform = et.ExtCompose(head + [
         et.ExtColorJitter(brightness=0.5, contrast=0.5, saturation=0.5),
         et.ExtRandomHorizontalFlip(),
         et.ExtToTensor(),

@@ -19,6 +19,14 @@ shuffle -> flip coin; ext_transforms.py:362-365, 483-499, 229) and runs two HIP 
 dml_aug_apply) that reproduce Pillow's arithmetic bit for bit.  Output: float32 NCHW images and int64 labels (the
 reference casts its uint8 labels to long right after the loader, main_embedding.py:463).
 There is no CPU fallback: inputs must be CUDA tensors and libdmlnet_hip.so must be present.
+
+The scale-augmented train block and the --crop_val block (main.py / main_embedding.py get_dataset of the reference)
+
+    [ExtRandomScale | ExtScale | ExtResize]  [ExtRandomCrop(padding, pad_if_needed) | ExtCenterCrop]  ...
+
+run one more kernel first (dml_aug_scale_window, utils/scale_window.py): per sample the frame resized to (Hs, Ws) is a
+virtual image, padding and cropping reduce to one window origin in it, and the kernel writes that uint8 window -- Pillow's
+BILINEAR for the image, its NEAREST for the label, 0 outside -- which the two kernels above then take as their frame.
 """
 import ctypes as C
 import numbers
@@ -27,13 +35,101 @@ import random
 import torch
 
 from dmlnet import _lib
+from . import scale_window
+
+BILINEAR = 2          # PIL.Image.BILINEAR
+
+
+def _check_interpolation(interpolation):
+    if interpolation != BILINEAR:
+        raise NotImplementedError("only interpolation=BILINEAR (2) is implemented; labels always use NEAREST")
+
+
+def _target(H, W, scale):
+    return int(H * scale), int(W * scale)
+
+
+class ExtRandomScale(object):
+    def __init__(self, scale_range, interpolation=BILINEAR):
+        _check_interpolation(interpolation)
+        self.scale_range = (scale_range[0], scale_range[1])
+        self.interpolation = interpolation
+
+    def get_size(self, H, W):
+        """(scale, (Hs, Ws)); one random.uniform per sample (ext_transforms.py:110-111)."""
+        scale = random.uniform(self.scale_range[0], self.scale_range[1])
+        return scale, _target(H, W, scale)
+
+
+class ExtScale(object):
+    def __init__(self, scale, interpolation=BILINEAR):
+        _check_interpolation(interpolation)
+        self.scale = scale
+        self.interpolation = interpolation
+
+    def get_size(self, H, W):
+        return self.scale, _target(H, W, self.scale)
+
+
+class ExtResize(object):
+    def __init__(self, size, interpolation=BILINEAR):
+        _check_interpolation(interpolation)
+        if isinstance(size, numbers.Integral) and not isinstance(size, bool):
+            self.size = int(size)
+        elif isinstance(size, (tuple, list)) and len(size) == 2:
+            self.size = (int(size[0]), int(size[1]))
+        else:
+            raise TypeError("ExtResize: size is an int or an (h, w) pair")
+        self.interpolation = interpolation
+
+    def get_size(self, H, W):
+        """torchvision 0.6.0 functional.resize: a pair is (h, w); an int is matched to the smaller edge (no-op when it
+        already has that size), the other edge becomes int(size * long / short)."""
+        if isinstance(self.size, tuple):
+            return None, self.size
+        size = self.size
+        if (W <= H and W == size) or (H <= W and H == size):
+            return None, (H, W)
+        if W < H:
+            return None, (int(size * H / W), size)
+        return None, (size, int(size * W / H))
+
+
+class ExtCenterCrop(object):
+    def __init__(self, size):
+        self.size = (int(size), int(size)) if isinstance(size, numbers.Number) else tuple(int(s) for s in size)
+
+    def get_params(self, img_hw):
+        """(i, j, th, tw) of torchvision 0.6.0 center_crop; negative when the crop is larger than the image."""
+        h, w = img_hw
+        th, tw = self.size
+        return int(round((h - th) / 2.)), int(round((w - tw) / 2.)), th, tw
 
 
 class ExtRandomCrop(object):
     def __init__(self, size, padding=0, pad_if_needed=False):
         self.size = (int(size), int(size)) if isinstance(size, numbers.Number) else tuple(int(s) for s in size)
-        if padding or pad_if_needed:
-            raise NotImplementedError("ExtRandomCrop padding is not used by the Cityscapes pipeline and not implemented")
+        if not (isinstance(padding, numbers.Integral) and padding >= 0):
+            raise NotImplementedError("ExtRandomCrop: padding is one non-negative int (all four borders)")
+        self.padding = int(padding)
+        self.pad_if_needed = bool(pad_if_needed)
+
+    def padded(self, img_hw):
+        """((h, w) after the pads, (py, px) = where the unpadded image's origin lies in the padded one), following
+        ext_transforms.py:378-390: `padding`, then ALL FOUR borders by int((1 + tw - w) / 2) if the width is short, then
+        the same test for the height on the already padded image."""
+        h, w = img_hw
+        th, tw = self.size
+        py = px = 0
+        if self.padding > 0:
+            h, w, py, px = h + 2 * self.padding, w + 2 * self.padding, py + self.padding, px + self.padding
+        if self.pad_if_needed and w < tw:
+            q = int((1 + tw - w) / 2)
+            h, w, py, px = h + 2 * q, w + 2 * q, py + q, px + q
+        if self.pad_if_needed and h < th:
+            q = int((1 + th - h) / 2)
+            h, w, py, px = h + 2 * q, w + 2 * q, py + q, px + q
+        return (h, w), (py, px)
 
     @staticmethod
     def get_params(img_hw, output_size):
@@ -96,7 +192,9 @@ class ExtNormalize(object):
 
 
 class ExtCompose(object):
-    """[ExtRandomCrop]? [ExtColorJitter]? [ExtRandomHorizontalFlip]? ExtToTensor ExtNormalize, fused on the device."""
+    """[ExtRandomScale | ExtScale | ExtResize]? [ExtRandomCrop | ExtCenterCrop]? [ExtColorJitter]? [ExtRandomHorizontalFlip]?
+    ExtToTensor ExtNormalize, fused on the device.  A sequence with a scale / resize stage, a centre crop or a padding random
+    crop runs dml_aug_scale_window first (`self.windowed`); any other sequence launches exactly the two kernels it always did."""
 
     def __init__(self, transforms, label_luts=None):
         """label_luts: optional (lut, lut_true) uint8[256] tables (datasets.Cityscapes.label_luts) -- the dataset's
@@ -105,25 +203,37 @@ class ExtCompose(object):
         self.transforms = list(transforms)
         self.label_luts = label_luts
         self._dev_luts = None
-        order = [ExtRandomCrop, ExtColorJitter, ExtRandomHorizontalFlip, ExtToTensor, ExtNormalize]
+        order = {ExtRandomScale: 0, ExtScale: 0, ExtResize: 0, ExtRandomCrop: 1, ExtCenterCrop: 1, ExtColorJitter: 2,
+                 ExtRandomHorizontalFlip: 3, ExtToTensor: 4, ExtNormalize: 5}
         pos = -1
-        self.crop = self.jitter = self.flip = self.norm = None
+        self.resize = self.crop = self.jitter = self.flip = self.norm = None
         seen_tensor = False
         for t in self.transforms:
-            if type(t) not in order or order.index(type(t)) <= pos:
+            if type(t) not in order or order[type(t)] <= pos:
                 raise NotImplementedError("unsupported transform sequence for the device pipeline: %r" % (t,))
-            pos = order.index(type(t))
-            if isinstance(t, ExtRandomCrop): self.crop = t
+            pos = order[type(t)]
+            if pos == 0: self.resize = t
+            elif pos == 1: self.crop = t
             elif isinstance(t, ExtColorJitter): self.jitter = t
             elif isinstance(t, ExtRandomHorizontalFlip): self.flip = t
             elif isinstance(t, ExtToTensor): seen_tensor = True
             elif isinstance(t, ExtNormalize): self.norm = t
         if not seen_tensor or self.norm is None:
             raise NotImplementedError("the device pipeline ends with ExtToTensor, ExtNormalize")
+        self.windowed = (self.resize is not None or isinstance(self.crop, ExtCenterCrop)
+                         or (self.crop is not None and (self.crop.padding > 0 or self.crop.pad_if_needed)))
         self.last_params = None
 
     def sample(self, B, H, W):
-        """One (i, j, ops, flip) per image, drawn in the reference's per-sample order."""
+        """One dict per image, drawn in the reference's per-sample order (scale, crop i, crop j -- none when the padded size
+        equals the crop size --, jitter factors, shuffle, flip coin), and the output size.  Keys: i, j (crop origin; in the
+        PADDED image when the crop pads), ops, flip.  A windowed sequence (see the class) adds
+          size    (Hs, Ws) of the resized frame, the virtual image
+          oy, ox  origin of the output window in the virtual image (negative: the window starts in the padding)
+          out     (th, tw) of the output window
+        and __call__(params=...) reads only size, oy, ox, out, ops and flip of those."""
+        if self.windowed:
+            return self._sample_windowed(B, H, W)
         out = []
         for _ in range(B):
             if self.crop is not None:
@@ -134,6 +244,47 @@ class ExtCompose(object):
             flip = self.flip is not None and random.random() < self.flip.p
             out.append({"i": i, "j": j, "ops": ops, "flip": bool(flip)})
         return out, (th, tw)
+
+    def _sample_windowed(self, B, H, W):
+        if isinstance(self.resize, ExtRandomScale) and self.crop is None and B > 1:
+            raise ValueError("ExtRandomScale on a batch needs a following crop: the outputs would differ in size")
+        out, size = [], None
+        for _ in range(B):
+            Hs, Ws = self.resize.get_size(H, W)[1] if self.resize is not None else (H, W)
+            if Hs <= 0 or Ws <= 0:
+                raise ValueError("the scaled frame is empty (%d x %d)" % (Hs, Ws))
+            if isinstance(self.crop, ExtRandomCrop):
+                hw, (py, px) = self.crop.padded((Hs, Ws))
+                i, j, th, tw = ExtRandomCrop.get_params(hw, self.crop.size)
+                oy, ox = i - py, j - px
+            elif isinstance(self.crop, ExtCenterCrop):
+                i, j, th, tw = self.crop.get_params((Hs, Ws))
+                oy, ox = i, j
+            else:
+                i = j = oy = ox = 0
+                th, tw = Hs, Ws
+            ops = self.jitter.get_params() if self.jitter is not None else []
+            flip = self.flip is not None and random.random() < self.flip.p
+            out.append({"i": i, "j": j, "ops": ops, "flip": bool(flip), "size": (Hs, Ws), "oy": oy, "ox": ox,
+                        "out": (th, tw)})
+            size = (th, tw)
+        return out, size
+
+    def _window(self, lib, img, lbl, params, st):
+        """dml_aug_scale_window: frames [B,H,W,3] (+ labels) -> the uint8 windows [B,th,tw,3] (+ [B,th,tw])."""
+        B, H, W, _ = img.shape
+        th, tw = params[0]["out"]
+        if any(tuple(p["out"]) != (th, tw) for p in params):
+            raise ValueError("the samples of one batch must share the output size")
+        buf, band, rows = scale_window.pack([(p["size"][0], p["size"][1], p["oy"], p["ox"]) for p in params], H, W, th, tw)
+        dev = torch.from_numpy(buf).to(img.device, non_blocking=False)
+        wimg = torch.empty((B, th, tw, 3), dtype=torch.uint8, device=img.device)
+        wlbl = torch.empty((B, th, tw), dtype=torch.uint8, device=img.device) if lbl is not None else None
+        _lib.check(lib.dml_aug_scale_window(img.data_ptr(), lbl.data_ptr() if lbl is not None else None, dev.data_ptr(),
+                                            dev.data_ptr(), buf.size, wimg.data_ptr(),
+                                            wlbl.data_ptr() if wlbl is not None else None, B, H, W, th, tw, band, rows, st),
+                   "dml_aug_scale_window")
+        return wimg, wlbl
 
     def __call__(self, img, lbl, params=None):
         lib = _lib.load()
@@ -148,15 +299,25 @@ class ExtCompose(object):
         if lbl is not None and (lbl.dtype != torch.uint8 or tuple(lbl.shape) != (B, H, W) or not lbl.is_contiguous()
                                 or lbl.device != img.device):
             raise ValueError("labels must be contiguous uint8 [B,H,W] on the frames' device")
+        st = torch.cuda.current_stream(img.device).cuda_stream
         if params is None:
             params, (th, tw) = self.sample(B, H, W)
+        elif len(params) != B:
+            raise ValueError("one parameter dict per frame")
+        elif self.windowed:
+            th, tw = params[0]["out"]
         else:
             th, tw = self.crop.size if self.crop is not None else (H, W)
         self.last_params = params
+        if self.windowed:
+            # the window is materialised (B * th * tw * 4 bytes): the contrast pivot is the mean over the crop
+            img, lbl = self._window(lib, img, lbl, params, st)
+            H, W = th, tw
         arr = (_lib.AugSample * B)()
         for b, p in enumerate(params):
             a = arr[b]
-            a.i, a.j, a.flip, a.n_ops = p["i"], p["j"], int(p["flip"]), len(p["ops"])
+            a.i, a.j = (0, 0) if self.windowed else (p["i"], p["j"])
+            a.flip, a.n_ops = int(p["flip"]), len(p["ops"])
             for k, (code, f) in enumerate(p["ops"]):
                 a.op[k], a.factor[k] = code, f
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
@@ -164,7 +325,6 @@ class ExtCompose(object):
         lsum = torch.empty(B, dtype=torch.int32, device=img.device)
         out = torch.empty((B, 3, th, tw), dtype=torch.float32, device=img.device)
         olb = torch.empty((B, th, tw), dtype=torch.int64, device=img.device) if lbl is not None else None
-        st = torch.cuda.current_stream(img.device).cuda_stream
         m, s = self.norm.mean, self.norm.std
         _lib.check(lib.dml_aug_contrast_sum(img.data_ptr(), dev_params.data_ptr(), lsum.data_ptr(), B, H, W, th, tw, st),
                    "dml_aug_contrast_sum")
