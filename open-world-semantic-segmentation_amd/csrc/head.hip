@@ -638,12 +638,14 @@ __global__ __launch_bounds__(256) void argmax_msp_kernel(const float* __restrict
 }
 
 // ---- dissum score: clip(-sum_k logit_k), then per-image min-max normalisation
+// The integer atomic is chosen by the SIGN BIT, not by `v >= 0.f`: -0.0f compares >= 0 but its bit pattern is INT_MIN, which
+// as a signed int never raises a stored maximum and replaces every stored negative minimum.
 __device__ __forceinline__ void atomic_min_f(float* addr, float v) {
-    if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMax(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
 }
 __device__ __forceinline__ void atomic_max_f(float* addr, float v) {
-    if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
 }
 __global__ void minmax_init_kernel(float* work, int B) {
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(256) void dissum_kernel(const float* __restrict__ l
         const float* src = logits + (int64_t)b * K * HW + pix;
         float s = 0.f;
         for (int k = 0; k < K; ++k) s += src[(int64_t)k * HW];
-        s = -s;
+        s = -s + 0.0f;                                          // a zero sum scores +0.0, never -0.0
         if (inclusive ? (s >= clip) : (s > clip)) s = clip;
         score[(int64_t)b * HW + pix] = s;
         lo = fminf(lo, s);

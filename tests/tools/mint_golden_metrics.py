@@ -1,8 +1,48 @@
-"""Mint tests/golden/g10_metrics.npz from the reference's StreamSegMetrics (authoring container only)."""
+"""Mint tests/golden/g10_metrics.npz from the reference's StreamSegMetrics (authoring container only).
+
+    python tests/tools/mint_golden_metrics.py              g10_metrics.npz and g11_ood_measures.npz
+    python tests/tools/mint_golden_metrics.py ood_edges    g11b_ood_edges.npz only (the other files are not touched)
+"""
 import contextlib, importlib.util, io, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.dont_write_bytecode = True
+
+
+def _ref_anom_utils():
+    spec = importlib.util.spec_from_file_location("ref_anom_utils", "/root/reference/anomaly/anom_utils.py")
+    au = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(au)
+    return au
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# G11b: the edge cases of tests/open_set_cases.py (P = 1, N = 1, ties, signed zeros, subnormals, +-FLT_MAX, recall levels,
+# eight out-labels, 8 M scores) through the reference's anom_utils.get_measures.  Results for every case; the inputs too
+# where they are small, so that a drift of the seeded generator shows as a fixture mismatch.
+# ---------------------------------------------------------------------------------------------------------------------
+def mint_ood_edges():
+    import warnings
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import open_set_cases as CS
+    au = _ref_anom_utils()
+    out = {}
+    for k, (pos, neg, recall) in CS.ood_cases().items():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)               # np.diff overflows between -FLT_MAX and FLT_MAX
+            a, p, f = au.get_measures(pos, neg, recall)
+        out[k + "_res"] = np.array([a, p, f], dtype=np.float64)
+        if len(pos) + len(neg) <= CS.OOD_STORE_INPUTS_UP_TO:
+            out[k + "_pos"], out[k + "_neg"] = pos, neg
+        print(k, len(pos), len(neg), recall, a, p, f)
+    assert set(k[:-4] for k in out if k.endswith("_res")) == set(CS.OOD_NAMES)
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "g11b_ood_edges.npz"), **out)
+
+
+if sys.argv[1:] == ["ood_edges"]:
+    mint_ood_edges()
+    sys.exit(0)
+
 spec = importlib.util.spec_from_file_location("ref_stream_metrics",
                                               "/root/reference/DeepLabV3Plus-Pytorch/metrics/stream_metrics.py")
 sm = importlib.util.module_from_spec(spec)
@@ -32,9 +72,7 @@ print(r["Overall Acc"], r["Mean IoU"], np.isnan(np.array(list(r["Class IoU"].val
 # average_precision_score, fpr_and_fdr_at_recall), as called by eval_ood_traditional.py:128-148
 # ---------------------------------------------------------------------------------------------------------------------
 def mint_ood():
-    spec = importlib.util.spec_from_file_location("ref_anom_utils", "/root/reference/anomaly/anom_utils.py")
-    au = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(au)
+    au = _ref_anom_utils()
     rs = np.random.RandomState(33)
     cases = {}
     # continuous scores, overlapping classes
