@@ -473,6 +473,26 @@ int dml_dissum_score(const float* logits, float* score, float* work, int B, int 
 /* preds[p] = new_label where -|f_p - proto|^2 > thresh and > max_k logits[k][p] */
 int dml_novel_relabel(const float* feats, const float* logits, const float* proto, int64_t* preds,
                       int B, int C, int K, int H, int W, float thresh, int64_t new_label, void* stream);
+/* The three calls above in one pass over logits[B,K,H,W] and feats[B,H,W,C], for N <= 8 few-shot prototypes
+ * (test_embedding.py:339-350,365,445 and the 2- / 3-class rules kept at :510-511,:520-522 of the reference):
+ *   preds = first maximal k (as dml_argmax_msp); msp = 1 - max softmax; score = dml_dissum_score's value (same clip
+ *   rule, +0.0 for a zero sum, per-image min / max left in work[2 b], work[2 b + 1], then normalised by a second launch);
+ *   d_j = -sum_c (f_c - protos[j][c])^2; with j* the index whose d is strictly above every other d_j (a tie for the top:
+ *   none), preds = new_labels[j*] iff d_j* > thresh and (vs_known == 0 or d_j* > max_k logit_k).
+ * N = 1, vs_known = 1 is dml_novel_relabel's rule; vs_known = 0 compares the novel distances only with each other.
+ * msp and score may be NULL (score != NULL needs work: 2 B floats).  N = 0 skips the relabel and never reads feats /
+ * protos / new_labels (they may be NULL).  protos [N,C] and new_labels [N] are device arrays.
+ * DML_EINVAL: a required pointer is NULL, or B, C, K, H, W <= 0, or N < 0.  DML_EUNSUPPORTED: C > 32, K > 33, N > 8,
+ * B > 65535 or B H W > 2^40.  16-byte loads (4 pixels per lane) when H W % 4 == 0 and the tensors are 16-byte aligned,
+ * one pixel per lane otherwise; C = K = 16 keeps logits and features in registers. */
+int dml_open_world_post(const float* logits, const float* feats, const float* protos, const int64_t* new_labels,
+                        int64_t* preds, float* msp, float* score, float* work, int B, int C, int K, int H, int W,
+                        int N, float thresh, int vs_known, float clip, int inclusive, void* stream);
+/* The relabel rule of dml_open_world_post alone, in place on given preds (a second instantiation of the same kernel:
+ * only relabelled pixels are written; the logits are read only when vs_known != 0).  Same checks and codes. */
+int dml_novel_relabel_multi(const float* feats, const float* logits, const float* protos, const int64_t* new_labels,
+                            int64_t* preds, int B, int C, int K, int H, int W, int N, float thresh, int vs_known,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DML loss = CE(-dist^2)/n + alpha * VAR/n (anomaly/models/models.py:42-78; live part of
@@ -642,6 +662,13 @@ int dml_confusion_update(const int64_t* label_true, const int64_t* label_pred, i
  * labels[p] == class_id, count (device uint64) = their number.  C <= 32. */
 int dml_class_feature_sum(const float* feats, const int64_t* labels, int64_t n_px, int C, int64_t class_id,
                           double* sums, unsigned long long* count, void* stream);
+/* The same for M <= 8 classes in one read of feats and labels: sums[m][c] (device double[M*C], zeroed by the call) and
+ * counts[m] (device uint64[M]) for class_ids[m] (device int64[M]).  The ids must be distinct: the library cannot see
+ * device memory, so the caller checks that (utils.extract_prototypes raises DML_EINVAL's error for duplicates).
+ * Accumulation as in dml_class_feature_sum (fp32 within a thread, at most ceil(n_px / 262144) terms; double across
+ * threads).  DML_EINVAL for a NULL pointer, n_px <= 0, C outside 1..32 or M outside 1..8. */
+int dml_class_feature_sums(const float* feats, const int64_t* labels, int64_t n_px, int C, const int64_t* class_ids,
+                           int M, double* sums, unsigned long long* counts, void* stream);
 
 /* Pixel-level OOD measures (anomaly/anom_utils.py:25-78 as called by eval_ood_traditional.py:128-148):
  * scores = -conf; positives = pixels whose label is one of out_labels (host array, n_out <= 8), negatives = the

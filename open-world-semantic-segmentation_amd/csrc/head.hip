@@ -715,6 +715,211 @@ __global__ __launch_bounds__(256) void novel_relabel_kernel(const float* __restr
     }
 }
 
+// ---- open-world post-processing in one pass: argmax, MSP, raw dissum (+ per-image range) and the relabel against up to
+// MAXN few-shot prototypes (test_embedding.py:339-350,365,445 and the 2- / 3-class rules at :510-511,:520-522 of the
+// reference).  One read of the logits, one of the features.  PX = 4: a lane owns 4 consecutive pixels, every logit plane is
+// read with one 16-byte load; PX = 1 serves H W % 4 != 0 and unaligned tensors.  FAST fixes C = K = 16: logits and the
+// four 64-byte feature rows stay in registers.  The generic path keeps nothing: it re-reads the logits for the softmax
+// denominator (as argmax_msp_kernel does) and the feature row per prototype; those hit in cache.
+// POST = false is novel_relabel_multi: given preds, only the relabelled pixels are written.
+constexpr int MAXN = 8;
+
+// 16-byte load of a stream that is read once (logits 134 MB, features 134 MB per 1024 x 2048 frame): NT marks it non-temporal
+template <bool NT> __device__ __forceinline__ float4 load4(const float* p) {
+    if constexpr (NT) {
+        typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+        const f32x4_nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
+        return make_float4(t.x, t.y, t.z, t.w);
+    } else {
+        return *reinterpret_cast<const float4*>(p);
+    }
+}
+
+template <int PX, bool NT> __device__ __forceinline__ void load_px(const float* p, float (&v)[PX]) {
+    if constexpr (PX == 4) {
+        const float4 t = load4<NT>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+
+// the strict winner among the prototype distances: `tie` when another one equals the best
+__device__ __forceinline__ void top_update(float d, int j, float& best, int& bj, bool& tie) {
+    if (j == 0 || d > best) { best = d; bj = j; tie = false; }
+    else if (d == best) tie = true;
+}
+
+template <int PX, bool FAST, bool POST, bool NT>
+__global__ __launch_bounds__(256) void open_world_post_kernel(const float* __restrict__ logits,
+                                                              const float* __restrict__ feats,
+                                                              const float* __restrict__ protos,
+                                                              const int64_t* __restrict__ new_labels,
+                                                              int64_t* __restrict__ preds, float* __restrict__ msp,
+                                                              float* __restrict__ score, float* work, int Cr, int Kr,
+                                                              int64_t HW, int N, float thresh, int vs_known, float clip,
+                                                              int inclusive) {
+    __shared__ __attribute__((aligned(16))) float sp[MAXN * MAXC];
+    __shared__ int64_t slab[MAXN];
+    __shared__ float smin[4], smax[4];
+    const int C = FAST ? 16 : Cr, K = FAST ? 16 : Kr;
+    if (threadIdx.x < N) slab[threadIdx.x] = new_labels[threadIdx.x];
+    load_protos(sp, protos, N * C);                                  // ends with the block barrier (N = 0: nothing read)
+    const int b = blockIdx.y;
+    const float* lg = logits + (int64_t)b * K * HW;
+    const bool need_logits = POST || vs_known;
+    float lo = INFINITY, hi = -INFINITY;
+    const int64_t groups = (HW + PX - 1) / PX;                       // PX = 4 runs only when HW % 4 == 0
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        const int64_t pix = g * PX, i = (int64_t)b * HW + pix;
+        float best[PX], sum[PX], den[PX];
+        int bi[PX];
+#pragma unroll
+        for (int p = 0; p < PX; ++p) { best[p] = -INFINITY; sum[p] = 0.f; den[p] = 0.f; bi[p] = 0; }
+        if (need_logits) {
+            if constexpr (FAST) {
+                float l[16][PX];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) load_px<PX, NT>(lg + (int64_t)k * HW + pix, l[k]);
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+#pragma unroll
+                    for (int p = 0; p < PX; ++p) {
+                        sum[p] += l[k][p];
+                        if (k == 0 || l[k][p] > best[p]) { best[p] = l[k][p]; bi[p] = k; }
+                    }
+                if (POST && msp != nullptr)
+#pragma unroll
+                    for (int k = 0; k < 16; ++k)
+#pragma unroll
+                        for (int p = 0; p < PX; ++p) den[p] += expf(l[k][p] - best[p]);
+            } else {
+                for (int k = 0; k < K; ++k) {
+                    float v[PX];
+                    load_px<PX, false>(lg + (int64_t)k * HW + pix, v);
+#pragma unroll
+                    for (int p = 0; p < PX; ++p) {
+                        sum[p] += v[p];
+                        if (k == 0 || v[p] > best[p]) { best[p] = v[p]; bi[p] = k; }
+                    }
+                }
+                if (POST && msp != nullptr)
+                    for (int k = 0; k < K; ++k) {
+                        float v[PX];
+                        load_px<PX, false>(lg + (int64_t)k * HW + pix, v);
+#pragma unroll
+                        for (int p = 0; p < PX; ++p) den[p] += expf(v[p] - best[p]);
+                    }
+            }
+        }
+        // relabel: the prototype that is strictly nearer than every other one, above the threshold (and the known classes)
+        float top[PX];
+        int tj[PX];
+        bool tie[PX];
+#pragma unroll
+        for (int p = 0; p < PX; ++p) { top[p] = -INFINITY; tj[p] = 0; tie[p] = false; }
+        if (N > 0) {
+            if constexpr (FAST) {
+                float f[PX][16];
+#pragma unroll
+                for (int p = 0; p < PX; ++p)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 t = load4<NT>(feats + (i + p) * 16 + q * 4);
+                        f[p][4 * q] = t.x; f[p][4 * q + 1] = t.y; f[p][4 * q + 2] = t.z; f[p][4 * q + 3] = t.w;
+                    }
+                // the prototype loop sits INSIDE the unrolled pixel loop, here and below: with the loops the other way
+                // round hipcc keeps the winner's index in a scalar register (one value per wave, set from the uniform
+                // loop counter only at j == 0) although the comparison that selects it is per lane, and every relabelled
+                // pixel gets new_labels[0]
+#pragma unroll
+                for (int p = 0; p < PX; ++p) {
+                    float tp = -INFINITY;
+                    int jp = 0;
+                    bool tp_tie = false;
+                    for (int j = 0; j < N; ++j) {
+                        float d = 0.f;
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) {
+                            const float t = f[p][c] - sp[j * 16 + c];     // same address in every lane: an LDS broadcast
+                            d += t * t;
+                        }
+                        top_update(-d, j, tp, jp, tp_tie);
+                    }
+                    top[p] = tp; tj[p] = jp; tie[p] = tp_tie;
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < PX; ++p) {
+                    const float* fr = feats + (i + p) * C;
+                    float tp = -INFINITY;
+                    int jp = 0;
+                    bool tp_tie = false;
+                    for (int j = 0; j < N; ++j) {
+                        float d = 0.f;
+                        for (int c = 0; c < C; ++c) {
+                            const float t = fr[c] - sp[j * C + c];
+                            d += t * t;
+                        }
+                        top_update(-d, j, tp, jp, tp_tie);
+                    }
+                    top[p] = tp; tj[p] = jp; tie[p] = tp_tie;
+                }
+            }
+        }
+        int64_t out[PX];
+        bool hit[PX];
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+            hit[p] = N > 0 && !tie[p] && top[p] > thresh && (!vs_known || top[p] > best[p]);
+            out[p] = hit[p] ? slab[tj[p]] : (int64_t)bi[p];
+        }
+        if constexpr (POST) {
+            if constexpr (PX == 4) {
+                typedef long long ll2 __attribute__((ext_vector_type(2)));
+                ll2* dst = reinterpret_cast<ll2*>(preds + i);
+                dst[0] = ll2{out[0], out[1]};
+                dst[1] = ll2{out[2], out[3]};
+                if (msp != nullptr)
+                    *reinterpret_cast<float4*>(msp + i) =
+                        make_float4(1.f - 1.f / den[0], 1.f - 1.f / den[1], 1.f - 1.f / den[2], 1.f - 1.f / den[3]);
+            } else {
+                preds[i] = out[0];
+                if (msp != nullptr) msp[i] = 1.f - 1.f / den[0];
+            }
+            if (score != nullptr) {
+                float s[PX];
+#pragma unroll
+                for (int p = 0; p < PX; ++p) {
+                    s[p] = -sum[p] + 0.0f;                            // a zero sum scores +0.0, never -0.0
+                    if (inclusive ? (s[p] >= clip) : (s[p] > clip)) s[p] = clip;
+                    lo = fminf(lo, s[p]);
+                    hi = fmaxf(hi, s[p]);
+                }
+                if constexpr (PX == 4) *reinterpret_cast<float4*>(score + i) = make_float4(s[0], s[1], s[2], s[3]);
+                else score[i] = s[0];
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < PX; ++p)
+                if (hit[p]) preds[i + p] = out[p];
+        }
+    }
+    if (POST && score != nullptr) {                                   // per-image range, as dissum_kernel leaves it
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = fminf(lo, __shfl_xor(lo, o, 64));
+            hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+        }
+        if ((threadIdx.x & 63) == 0) { smin[threadIdx.x >> 6] = lo; smax[threadIdx.x >> 6] = hi; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 4; ++w) { lo = fminf(lo, smin[w]); hi = fmaxf(hi, smax[w]); }
+            if (lo <= hi) { atomic_min_f(work + 2 * b, lo); atomic_max_f(work + 2 * b + 1, hi); }
+        }
+    }
+}
+
 // ---- DML loss
 // block partial = (sum nll, #valid, sum -logit_y over valid, #correct)
 template <int PX>
@@ -1239,6 +1444,69 @@ extern "C" int dml_novel_relabel(const float* feats, const float* logits, const 
     return 0;
 }
 
+namespace {
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// argument checks shared by dml_open_world_post and dml_novel_relabel_multi
+int open_world_check(const float* logits, const float* feats, const float* protos, const int64_t* new_labels,
+                     const int64_t* preds, int B, int C, int K, int H, int W, int N) {
+    if (!logits || !preds || B <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || N < 0) return DML_EINVAL;
+    if (N > 0 && (!feats || !protos || !new_labels)) return DML_EINVAL;
+    if (C > MAXC || K > MAXK || N > MAXN) return DML_EUNSUPPORTED;
+    // the image index is the grid's y; 2^40 pixels keep every element offset (x K, x C, x 8 bytes) inside int64
+    if (B > 65535 || (int64_t)B * H * W > (1ll << 40)) return DML_EUNSUPPORTED;
+    return 0;
+}
+
+template <bool POST>
+void open_world_launch(const float* logits, const float* feats, const float* protos, const int64_t* new_labels,
+                       int64_t* preds, float* msp, float* score, float* work, int B, int C, int K, int64_t HW, int N,
+                       float thresh, int vs_known, float clip, int inclusive, hipStream_t st) {
+    // the generic 4-pixel path reads the feature rows with scalar loads: only the register path needs them aligned
+    const bool vec = HW % 4 == 0 && aligned16(logits) && aligned16(preds) && aligned16(msp) && aligned16(score);
+    const dim3 grid(grid_for(vec ? HW / 4 : HW, 256, 4096), B);
+    if (vec && C == 16 && K == 16 && (N == 0 || aligned16(feats)))
+        hipLaunchKernelGGL((open_world_post_kernel<4, true, POST, DIST_NT_DEFAULT>), grid, dim3(256), 0, st, logits, feats,
+                           protos, new_labels, preds, msp, score, work, C, K, HW, N, thresh, vs_known, clip, inclusive);
+    else if (vec)
+        hipLaunchKernelGGL((open_world_post_kernel<4, false, POST, false>), grid, dim3(256), 0, st, logits, feats, protos,
+                           new_labels, preds, msp, score, work, C, K, HW, N, thresh, vs_known, clip, inclusive);
+    else
+        hipLaunchKernelGGL((open_world_post_kernel<1, false, POST, false>), grid, dim3(256), 0, st, logits, feats, protos,
+                           new_labels, preds, msp, score, work, C, K, HW, N, thresh, vs_known, clip, inclusive);
+}
+}  // namespace
+
+extern "C" int dml_open_world_post(const float* logits, const float* feats, const float* protos,
+                                   const int64_t* new_labels, int64_t* preds, float* msp, float* score, float* work,
+                                   int B, int C, int K, int H, int W, int N, float thresh, int vs_known, float clip,
+                                   int inclusive, void* stream) {
+    const int rc = open_world_check(logits, feats, protos, new_labels, preds, B, C, K, H, W, N);
+    if (rc != 0) return rc;
+    if (score && !work) return DML_EINVAL;
+    const int64_t HW = (int64_t)H * W;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (score) hipLaunchKernelGGL(minmax_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, work, B);
+    open_world_launch<true>(logits, feats, protos, new_labels, preds, msp, score, work, B, C, K, HW, N, thresh, vs_known,
+                            clip, inclusive, st);
+    if (score)
+        hipLaunchKernelGGL(minmax_norm_kernel, dim3(grid_for(HW, 256, 1024), B), dim3(256), 0, st, score, work, HW);
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dml_novel_relabel_multi(const float* feats, const float* logits, const float* protos,
+                                       const int64_t* new_labels, int64_t* preds, int B, int C, int K, int H, int W,
+                                       int N, float thresh, int vs_known, void* stream) {
+    const int rc = open_world_check(logits, feats, protos, new_labels, preds, B, C, K, H, W, N);
+    if (rc != 0) return rc;
+    if (N == 0) return 0;
+    open_world_launch<false>(logits, feats, protos, new_labels, preds, nullptr, nullptr, nullptr, B, C, K, (int64_t)H * W,
+                             N, thresh, vs_known, 0.f, 0, static_cast<hipStream_t>(stream));
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
 #define DML_LOSS_BLOCKS 2048
 
 extern "C" int dml_loss_fwd(const float* logits, const int64_t* labels, double* sums, float* block_partials,
@@ -1372,6 +1640,104 @@ extern "C" int dml_class_feature_sum(const float* feats, const int64_t* labels, 
         return DML_EINVAL;
     hipLaunchKernelGGL(class_feature_sum_kernel, dim3(grid_for(n_px, 256, 1024)), dim3(256), 0, st, feats, labels, n_px, C,
                        class_id, sums, count);
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same for up to MAXM classes in one read of the features and labels (the shots of the 16+2 / 16+3 settings).
+// QUADS lanes share a pixel, each owns 4 channels (one 16-byte load when C % 4 == 0), so a thread carries MAXM x 4 fp32
+// partial sums instead of MAXM x C.  Accumulation as above: fp32 within a thread, double across threads.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int MAXM = 8;
+
+template <int QUADS, bool VEC>
+__global__ __launch_bounds__(256) void class_feature_sums_kernel(const float* __restrict__ feats, const int64_t* __restrict__ labels,
+                                                                 int64_t n_px, int C, const int64_t* __restrict__ class_ids, int M,
+                                                                 double* __restrict__ sums, unsigned long long* __restrict__ counts) {
+    __shared__ double sh[MAXM * MAXC];
+    __shared__ unsigned long long shn[MAXM];
+    for (int i = threadIdx.x; i < MAXM * MAXC; i += 256) sh[i] = 0.0;
+    if (threadIdx.x < MAXM) shn[threadIdx.x] = 0ull;
+    __syncthreads();
+    int64_t ids[MAXM];
+#pragma unroll
+    for (int m = 0; m < MAXM; ++m) ids[m] = class_ids[m < M ? m : 0];
+    float acc[MAXM][4];
+    unsigned n[MAXM];
+#pragma unroll
+    for (int m = 0; m < MAXM; ++m) {
+        n[m] = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[m][e] = 0.f;
+    }
+    constexpr int SLOTS = 256 / QUADS;                               // pixels a workgroup reads per iteration
+    const int q = threadIdx.x % QUADS, c0 = 4 * q;
+    for (int64_t p = (int64_t)blockIdx.x * SLOTS + threadIdx.x / QUADS; p < n_px; p += (int64_t)gridDim.x * SLOTS) {
+        const int64_t lab = labels[p];
+        float f[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (VEC) {
+            if (c0 < C) {
+                const float4 t = *reinterpret_cast<const float4*>(feats + p * C + c0);
+                f[0] = t.x; f[1] = t.y; f[2] = t.z; f[3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c0 + e < C) f[e] = feats[p * C + c0 + e];
+        }
+#pragma unroll
+        for (int m = 0; m < MAXM; ++m)
+            if (m < M && lab == ids[m]) {
+                ++n[m];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[m][e] += f[e];
+            }
+    }
+#pragma unroll
+    for (int m = 0; m < MAXM; ++m)
+        if (n[m]) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c0 + e < C) atomicAdd(&sh[m * MAXC + c0 + e], (double)acc[m][e]);
+            if (q == 0) atomicAdd(&shn[m], (unsigned long long)n[m]);
+        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < M * MAXC; i += 256) {
+        const int m = i / MAXC, c = i % MAXC;
+        if (c < C && sh[i] != 0.0) atomicAdd(sums + m * C + c, sh[i]);
+    }
+    if (threadIdx.x < M && shn[threadIdx.x]) atomicAdd(counts + threadIdx.x, shn[threadIdx.x]);
+}
+}  // namespace
+
+extern "C" int dml_class_feature_sums(const float* feats, const int64_t* labels, int64_t n_px, int C,
+                                      const int64_t* class_ids, int M, double* sums, unsigned long long* counts,
+                                      void* stream) {
+    if (!feats || !labels || !class_ids || !sums || !counts || n_px <= 0 || C <= 0 || C > MAXC || M <= 0 || M > MAXM)
+        return DML_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(sums, 0, sizeof(double) * M * C, st) != hipSuccess || hipMemsetAsync(counts, 0, 8 * M, st) != hipSuccess)
+        return DML_EINVAL;
+    // 1024 x 256 pixel slots at most, as the single-class kernel: a thread's fp32 partial has ceil(n_px / 262144) terms
+    const int quads = C <= 4 ? 1 : C <= 8 ? 2 : C <= 16 ? 4 : 8;
+    const dim3 grid(grid_for(n_px * quads, 256, 1024 * quads));
+    const bool vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(feats) & 15) == 0;
+#define DML_FSUMS(Q)                                                                                                         \
+    do {                                                                                                                     \
+        if (vec)                                                                                                             \
+            hipLaunchKernelGGL((class_feature_sums_kernel<Q, true>), grid, dim3(256), 0, st, feats, labels, n_px, C,         \
+                               class_ids, M, sums, counts);                                                                  \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((class_feature_sums_kernel<Q, false>), grid, dim3(256), 0, st, feats, labels, n_px, C,        \
+                               class_ids, M, sums, counts);                                                                  \
+    } while (0)
+    if (quads == 1) DML_FSUMS(1);
+    else if (quads == 2) DML_FSUMS(2);
+    else if (quads == 4) DML_FSUMS(4);
+    else DML_FSUMS(8);
+#undef DML_FSUMS
     DML_LAUNCH_CHECK();
     return 0;
 }

@@ -97,6 +97,8 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_argmax_msp),
     DML_ENTRY(dml_dissum_score),
     DML_ENTRY(dml_novel_relabel),
+    DML_ENTRY(dml_open_world_post),
+    DML_ENTRY(dml_novel_relabel_multi),
     DML_ENTRY(dml_loss_fwd),
     DML_ENTRY(dml_loss_finalize),
     DML_ENTRY(dml_loss_bwd),
@@ -108,6 +110,7 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_upsample_nhwc_to_nchw),
     DML_ENTRY(dml_confusion_update),
     DML_ENTRY(dml_class_feature_sum),
+    DML_ENTRY(dml_class_feature_sums),
     DML_ENTRY(dml_label_encode),
     DML_ENTRY(dml_h2_split),
     DML_ENTRY(dml_h2_bound_bn),

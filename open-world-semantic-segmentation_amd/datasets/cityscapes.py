@@ -132,9 +132,16 @@ class Cityscapes(object):
     @staticmethod
     def eval_relabel_lut(held_out=13, new_id=16):
         """Table for the evaluation-time relabel of test_embedding.py:448-451 (held-out class -> new_id, every id above
-        it moves down by one, and the 254 that 255 became goes back to 255), composable with label_luts: lut2[lut[raw]]."""
+        it moves down by one, and the 254 that 255 became goes back to 255), composable with label_luts: lut2[lut[raw]].
+        Equal-length sequences give the 2- and 3-class tables the reference keeps at :512-517 and :523-530:
+        held_out[i] -> new_id[i], every other id below 255 moves down by the number of held-out ids below it."""
+        if np.ndim(held_out) == 0 and np.ndim(new_id) == 0:
+            held_out, new_id = [held_out], [new_id]
+        held, new = [int(h) for h in held_out], [int(n) for n in new_id]
+        if len(held) != len(new) or len(set(held)) != len(held) or not all(0 <= h < 255 for h in held):
+            raise ValueError("held_out and new_id must be equally long, the held-out ids distinct and below 255")
         t = np.arange(256, dtype=np.int64)
-        out = np.where(t > held_out, t - 1, t)
-        out[held_out] = new_id
-        out[out == 254] = 255
+        out = t - sum((t > h).astype(np.int64) for h in held)
+        out[255] = 255
+        out[held] = new
         return out.astype(np.uint8)

@@ -172,6 +172,9 @@ _PROTOS = {
     "dml_argmax_msp": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "dml_dissum_score": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dml_novel_relabel": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i64, c_p]),
+    "dml_open_world_post": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i,
+                                  c_p]),
+    "dml_novel_relabel_multi": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dml_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_p]),
     "dml_loss_finalize": (c_i, [c_p, c_p, c_f, c_f, c_p]),
     "dml_loss_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_p]),
@@ -180,6 +183,7 @@ _PROTOS = {
     "dml_convert_dtype": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),
     "dml_confusion_update": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p]),
     "dml_class_feature_sum": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_p, c_p, c_p]),
+    "dml_class_feature_sums": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p]),
     "dml_ood_workspace_bytes": (c_i64, [c_i64]),
     "dml_ood_measures": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i, C.c_double, c_p, c_i64, c_p, c_p]),
     "dml_aug_contrast_sum": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

@@ -85,3 +85,105 @@ def extract_prototype(features: torch.Tensor, labels_true: torch.Tensor, class_i
     if n == 0 or n / f.shape[0] <= min_fraction:
         return None
     return (sums / n).float().cpu().tolist()
+
+
+def _protos_labels(protos, new_labels, device):
+    """[N, C] float32 prototypes and [N] int64 labels on the device; (None, None, 0) for no prototype"""
+    if protos is None:
+        if new_labels is not None and len(new_labels):
+            raise ValueError("new_labels without protos")
+        return None, None, 0
+    if isinstance(protos, torch.Tensor):
+        pr = protos.to(device=device, dtype=torch.float32)
+    else:
+        pr = torch.as_tensor(np.asarray(protos, dtype=np.float32), device=device)
+    if pr.dim() != 2:
+        raise ValueError("protos must be [N, C]")
+    N = pr.shape[0]
+    lab = torch.as_tensor(np.asarray(new_labels if new_labels is not None else [], dtype=np.int64).reshape(-1), device=device)
+    if lab.numel() != N:
+        raise ValueError("one new label per prototype: %d prototypes, %d labels" % (N, lab.numel()))
+    if N == 0:
+        return None, None, 0
+    return pr.contiguous(), lab, N
+
+
+def open_world_post(logits: torch.Tensor, feats: torch.Tensor, protos=None, new_labels=None, thresh=-1.5,
+                    vs_known=True, clip=1000.0, inclusive=False, want_msp=True, want_score=True):
+    """argmax_msp + dissum_score + the relabel against N <= 8 few-shot prototypes in one pass over the logits and one
+    over the features (dml_open_world_post).  protos [N, C], new_labels [N]: prototype j relabels a pixel to
+    new_labels[j] when its -|f - p_j|^2 is strictly above every other prototype's, above `thresh` and -- with
+    vs_known -- above the best known-class logit (test_embedding.py:445; vs_known=False is the text of the 2- and
+    3-class rules at :510-511,:520-522).  Returns (preds, msp, score); msp / score are None when not wanted."""
+    _need_cuda(logits)
+    lib = _lib.load()
+    logits = logits.contiguous().float()
+    B, K, H, W = logits.shape
+    pr, lab, N = _protos_labels(protos, new_labels, logits.device)
+    if N:
+        feats = feats.contiguous().float()
+        C = feats.shape[-1]
+        if pr.shape[1] != C or feats.numel() != B * H * W * C:
+            raise ValueError("feats must be [B, H, W, C] and protos [N, C]")
+    else:
+        C = int(feats.shape[-1]) if feats is not None else 1
+    dev = logits.device
+    preds = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+    msp = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_msp else None
+    score = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_score else None
+    work = torch.empty(2 * B, dtype=torch.float32, device=dev) if want_score else None
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    _lib.check(lib.dml_open_world_post(logits.data_ptr(), ptr(feats) if N else None, ptr(pr), ptr(lab), preds.data_ptr(),
+                                       ptr(msp), ptr(score), ptr(work), B, C, K, H, W, N, float(thresh),
+                                       1 if vs_known else 0, float(clip), 1 if inclusive else 0, _st(logits)),
+               "dml_open_world_post")
+    return preds, msp, score
+
+
+def novel_relabel_multi(preds: torch.Tensor, logits: torch.Tensor, feats: torch.Tensor, protos, new_labels, thresh=-1.5,
+                        vs_known=True) -> torch.Tensor:
+    """In place, for callers that already hold predictions: open_world_post's relabel rule alone."""
+    _need_cuda(logits)
+    lib = _lib.load()
+    logits, feats = logits.contiguous().float(), feats.contiguous().float()
+    B, K, H, W = logits.shape
+    C = feats.shape[-1]
+    pr, lab, N = _protos_labels(protos, new_labels, logits.device)
+    if N and (pr.shape[1] != C or feats.numel() != B * H * W * C):
+        raise ValueError("feats must be [B, H, W, C] and protos [N, C]")
+    assert preds.is_contiguous() and preds.dtype == torch.int64 and preds.numel() == B * H * W
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    _lib.check(lib.dml_novel_relabel_multi(feats.data_ptr(), logits.data_ptr(), ptr(pr), ptr(lab), preds.data_ptr(), B, C,
+                                           K, H, W, N, float(thresh), 1 if vs_known else 0, _st(logits)),
+               "dml_novel_relabel_multi")
+    return preds
+
+
+def extract_prototypes(features: torch.Tensor, labels_true: torch.Tensor, class_ids, min_fraction: float = 0.05):
+    """extract_prototype for up to 8 classes in one read of the features and one device -> host copy:
+    {class_id: shot (list of C floats) or None when the class covers at most `min_fraction` of the pixels}."""
+    _need_cuda(features)
+    lib = _lib.load()
+    ids = [int(c) for c in class_ids]
+    if len(set(ids)) != len(ids):
+        _lib.check(-1, "dml_class_feature_sums (duplicate class ids)")
+    f = features.contiguous().float()
+    C = f.shape[-1]
+    f = f.view(-1, C)
+    lab = labels_true.contiguous().view(-1)
+    if lab.dtype != torch.int64 or lab.numel() != f.shape[0] or not lab.is_cuda:
+        raise ValueError("labels_true must be an int64 CUDA tensor with one entry per pixel of `features`")
+    M = len(ids)
+    # sums [M, C] and the counts behind them in one double buffer, so that a single copy brings both to the host
+    buf = torch.empty(M * C + M, dtype=torch.float64, device=f.device)
+    cid = torch.tensor(ids, dtype=torch.int64, device=f.device)
+    _lib.check(lib.dml_class_feature_sums(f.data_ptr(), lab.data_ptr(), f.shape[0], C, cid.data_ptr(), M, buf.data_ptr(),
+                                          buf.data_ptr() + 8 * M * C, _st(f)), "dml_class_feature_sums")
+    host = buf.cpu().numpy()
+    sums, counts = host[:M * C].reshape(M, C), host[M * C:].view(np.uint64)
+    out = {}
+    for m, c in enumerate(ids):
+        n = int(counts[m])
+        out[c] = None if n == 0 or n / f.shape[0] <= min_fraction else \
+            torch.from_numpy(sums[m] / n).float().tolist()
+    return out
