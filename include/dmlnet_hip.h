@@ -450,6 +450,31 @@ int dml_proto_dist_fwd(const float* x_nchw, const float* protos, float* logits, 
 int dml_upsample_dist_fwd(const float* e, const float* protos, float* logits, float* feats,
                           uint8_t* argmax, float* dissum, int B, int h, int w, int C, int K, int H,
                           int W, void* stream);
+/* Merged prediction of the incremental multi-head model (test_self_distillation.py:292-297) from the heads' low-resolution
+ * embeddings, in one pass and without full-resolution logits or features: 8 bytes written per pixel.
+ *   heads: HOST array of n descriptors (copied into the launch; the `e` inside are device pointers): e = embedding
+ *          [B,h,w,ld] NHWC fp32 -- what dml_upsample_dist_fwd takes --, C = channels carried (C <= ld; columns C..ld-1 are
+ *          never read), K = prototypes, novel_id = the class this head contributes (unused for head 0).
+ *   Per output pixel and head: f = bilinear sample of e at (H,W), align_corners = False, dml_upsample_dist_fwd's source
+ *   coordinates and weights; a_i = first maximal k of d_k = -sum_c (f_c - P[k][c])^2 over k < K, with P = 3 I_K cut to C
+ *   columns (Engine.prototypes; row C of a K = C + 1 head is zero).  Because d_k = 6 f_k - 9 - sum_c f_c^2 the kernel compares
+ *   the f_k (1.5 for k = C) and never rounds a distance: exact ties of f are exact ties of d, lowest k wins.
+ *   preds[B,H,W] (int64) = a_0, then for i = 1 .. n-1 in order: a_i == heads[i].novel_id -> preds = novel_id (a later head
+ *   overrides an earlier one; any other a_i changes nothing).  head_argmax: optional [n,B,H,W] uint8 = a_i; NULL skips it.
+ *   Any H, W >= 1 for any h, w >= 1.  preds is stored as 16-byte pairs from its first 16-byte boundary on, single values
+ *   before it and after the last whole pair; embedding rows are read as 16-byte vectors when C % 4 == 0, ld % 4 == 0 and e
+ *   is 16-byte aligned, as scalars otherwise.
+ * DML_EINVAL: heads or preds NULL, n < 1, B / h / w / H / W <= 0, or a head with e NULL, C <= 0, K <= 0 or ld < C.
+ * DML_EUNSUPPORTED: n > DML_PREDICT_MAX_HEADS, or a head with C > 32, K > 33 or K > C + 1 (prototype k lives in channel k:
+ *   beyond k = C it has no channel to be compared in).  DML_EALIGN: preds not 8-byte aligned.
+ * Nothing is written when a code is returned. */
+#define DML_PREDICT_MAX_HEADS 4
+typedef struct DmlPredictHead {
+    const float* e;
+    int32_t C, K, ld, novel_id;
+} DmlPredictHead;
+int dml_incremental_predict(const DmlPredictHead* heads, int n, int64_t* preds, uint8_t* head_argmax, int B, int h, int w,
+                            int H, int W, void* stream);
 /* df[b,h,w,c] = -2 * sum_k glogits[b,k,h,w] * (feats[b,h,w,c]-protos[k][c]) (+ gfeats[b,h,w,c]) */
 int dml_proto_dist_bwd(const float* glogits, const float* gfeats, const float* feats,
                        const float* protos, float* df, int B, int C, int K, int H, int W, void* stream);

@@ -28,6 +28,27 @@ template <bool NT> __device__ __forceinline__ void store4(float* p, const float4
     }
 }
 
+// ---- bilinear resize, align_corners = False (F.interpolate at network/utils.py:88): the two source taps of output
+// index I on an axis of n samples at scale s = n / N, and the blend of the four samples they select.  Every kernel that
+// resizes the embedding goes through these two, so they all see the same coordinates and weights.
+struct Tap {
+    int i0, i1;        // clamped neighbours (i1 == i0 on the last sample)
+    float l0, l1;      // their weights
+};
+__device__ __forceinline__ Tap src_tap(float s, int I, int n) {
+    float sI = s * ((float)I + 0.5f) - 0.5f;
+    sI = sI < 0.f ? 0.f : sI;
+    Tap t;
+    t.i0 = min((int)sI, n - 1);
+    t.i1 = t.i0 + (t.i0 < n - 1 ? 1 : 0);
+    t.l1 = sI - (float)t.i0;
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+__device__ __forceinline__ float bilerp(const Tap& ty, const Tap& tx, float a, float b, float c, float d) {
+    return ty.l0 * (tx.l0 * a + tx.l1 * b) + ty.l1 * (tx.l0 * c + tx.l1 * d);
+}
+
 __device__ __forceinline__ void load_protos(float* sp, const float* __restrict__ protos, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) sp[i] = protos[i];
     __syncthreads();
@@ -221,30 +242,23 @@ __global__ __launch_bounds__(256) void upsample_dist_fwd_c16_kernel(const float*
     const int b = (int)(ic / groups_per_img);
     const int64_t g = ic - (int64_t)b * groups_per_img;
     const int Y = (int)(g / WG), xg = (int)(g - (int64_t)Y * WG);
-    float sY = sy * ((float)Y + 0.5f) - 0.5f;
-    sY = sY < 0.f ? 0.f : sY;
-    const int y0 = min((int)sY, h - 1), y1 = y0 + (y0 < h - 1 ? 1 : 0);
-    const float ly1 = sY - (float)y0, ly0 = 1.f - ly1;
-    const float* r0 = e + ((int64_t)b * h + y0) * w * C;
-    const float* r1 = e + ((int64_t)b * h + y1) * w * C;
+    const Tap ty = src_tap(sy, Y, h);
+    const float* r0 = e + ((int64_t)b * h + ty.i0) * w * C;
+    const float* r1 = e + ((int64_t)b * h + ty.i1) * w * C;
     float f[C][4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int X = xg * 4 + p;
-        float sX = sx * ((float)X + 0.5f) - 0.5f;
-        sX = sX < 0.f ? 0.f : sX;
-        const int x0 = min((int)sX, w - 1), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-        const float lx1 = sX - (float)x0, lx0 = 1.f - lx1;
+        const Tap tx = src_tap(sx, xg * 4 + p, w);
 #pragma unroll
         for (int c = 0; c < C; c += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(r0 + x0 * C + c);
-            const float4 bq = *reinterpret_cast<const float4*>(r0 + x1 * C + c);
-            const float4 cq = *reinterpret_cast<const float4*>(r1 + x0 * C + c);
-            const float4 d = *reinterpret_cast<const float4*>(r1 + x1 * C + c);
-            f[c][p] = ly0 * (lx0 * a.x + lx1 * bq.x) + ly1 * (lx0 * cq.x + lx1 * d.x);
-            f[c + 1][p] = ly0 * (lx0 * a.y + lx1 * bq.y) + ly1 * (lx0 * cq.y + lx1 * d.y);
-            f[c + 2][p] = ly0 * (lx0 * a.z + lx1 * bq.z) + ly1 * (lx0 * cq.z + lx1 * d.z);
-            f[c + 3][p] = ly0 * (lx0 * a.w + lx1 * bq.w) + ly1 * (lx0 * cq.w + lx1 * d.w);
+            const float4 a = *reinterpret_cast<const float4*>(r0 + tx.i0 * C + c);
+            const float4 bq = *reinterpret_cast<const float4*>(r0 + tx.i1 * C + c);
+            const float4 cq = *reinterpret_cast<const float4*>(r1 + tx.i0 * C + c);
+            const float4 d = *reinterpret_cast<const float4*>(r1 + tx.i1 * C + c);
+            f[c][p] = bilerp(ty, tx, a.x, bq.x, cq.x, d.x);
+            f[c + 1][p] = bilerp(ty, tx, a.y, bq.y, cq.y, d.y);
+            f[c + 2][p] = bilerp(ty, tx, a.z, bq.z, cq.z, d.z);
+            f[c + 3][p] = bilerp(ty, tx, a.w, bq.w, cq.w, d.w);
         }
     }
     if (feats != nullptr) wave_store_nhwc16<NT>(stage[wave], f, feats, lane, wave_first, total);
@@ -300,10 +314,9 @@ __global__ __launch_bounds__(256) void upsample4_dist_fwd_c16_kernel(const float
     __syncthreads();
     const int Y = 4 * jb + 2 + wave;
     if (Y < 0 || Y >= H) return;                                          // (whole waves: no barrier below)
-    float sY = 0.25f * ((float)Y + 0.5f) - 0.5f;
-    sY = sY < 0.f ? 0.f : sY;
-    const int y0 = min((int)sY, h - 1);
-    const float ly1 = sY - (float)y0, ly0 = 1.f - ly1;
+    const Tap ty = src_tap(0.25f, Y, h);
+    const int y0 = ty.i0;
+    const float ly1 = ty.l1, ly0 = ty.l0;
     // y0 is r0 except on the last band's clamp, y1 = y0 + 1 clamped is r1 -- or both rows coincide
     const int ra = (y0 == r0) ? 0 : 1, rb = (min(y0 + 1, h - 1) == r1) ? 1 : 0;
     const int q = Q0 + lane;                                              // this lane's low-resolution column
@@ -325,11 +338,9 @@ __global__ __launch_bounds__(256) void upsample4_dist_fwd_c16_kernel(const float
     float f[C][4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int X = 4 * q + p;
-        float sX = 0.25f * ((float)X + 0.5f) - 0.5f;
-        sX = sX < 0.f ? 0.f : sX;
-        const int x0 = min((int)sX, w - 1), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-        const float l1 = sX - (float)x0, l0 = 1.f - l1;
+        const Tap tx = src_tap(0.25f, 4 * q + p, w);
+        const int x0 = tx.i0, x1 = tx.i1;
+        const float l1 = tx.l1, l0 = tx.l0;
         const float wl = (x0 == q - 1 ? l0 : 0.f) + (x1 == q - 1 ? l1 : 0.f);
         const float wc = (x0 == q ? l0 : 0.f) + (x1 == q ? l1 : 0.f);
         const float wr = (x0 == q + 1 ? l0 : 0.f) + (x1 == q + 1 ? l1 : 0.f);
@@ -492,46 +503,141 @@ __global__ __launch_bounds__(256) void upsample_dist_fwd_kernel(const float* __r
         int64_t t = i / WG;
         const int Y = (int)(t % H);
         const int b = (int)(t / H);
-        float sY = sy * ((float)Y + 0.5f) - 0.5f;
-        sY = sY < 0.f ? 0.f : sY;
-        const int y0 = min((int)sY, h - 1), y1 = y0 + (y0 < h - 1 ? 1 : 0);
-        const float ly1 = sY - (float)y0, ly0 = 1.f - ly1;
-        const float* r0 = e + ((int64_t)b * h + y0) * w * C;
-        const float* r1 = e + ((int64_t)b * h + y1) * w * C;
+        const Tap ty = src_tap(sy, Y, h);
+        const float* r0 = e + ((int64_t)b * h + ty.i0) * w * C;
+        const float* r1 = e + ((int64_t)b * h + ty.i1) * w * C;
         float f[CM][PX];
 #pragma unroll
         for (int p = 0; p < PX; ++p) {
-            const int X = xg * PX + p;
-            float sX = sx * ((float)X + 0.5f) - 0.5f;
-            sX = sX < 0.f ? 0.f : sX;
-            const int x0 = min((int)sX, w - 1), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-            const float lx1 = sX - (float)x0, lx0 = 1.f - lx1;
+            const Tap tx = src_tap(sx, xg * PX + p, w);
             if ((C & 3) == 0) {
 #pragma unroll
                 for (int c = 0; c < CM; c += 4) {
                     if (c < C) {
-                        const float4 a = *reinterpret_cast<const float4*>(r0 + x0 * C + c);
-                        const float4 bq = *reinterpret_cast<const float4*>(r0 + x1 * C + c);
-                        const float4 cq = *reinterpret_cast<const float4*>(r1 + x0 * C + c);
-                        const float4 d = *reinterpret_cast<const float4*>(r1 + x1 * C + c);
-                        f[c][p] = ly0 * (lx0 * a.x + lx1 * bq.x) + ly1 * (lx0 * cq.x + lx1 * d.x);
-                        f[c + 1][p] = ly0 * (lx0 * a.y + lx1 * bq.y) + ly1 * (lx0 * cq.y + lx1 * d.y);
-                        f[c + 2][p] = ly0 * (lx0 * a.z + lx1 * bq.z) + ly1 * (lx0 * cq.z + lx1 * d.z);
-                        f[c + 3][p] = ly0 * (lx0 * a.w + lx1 * bq.w) + ly1 * (lx0 * cq.w + lx1 * d.w);
+                        const float4 a = *reinterpret_cast<const float4*>(r0 + tx.i0 * C + c);
+                        const float4 bq = *reinterpret_cast<const float4*>(r0 + tx.i1 * C + c);
+                        const float4 cq = *reinterpret_cast<const float4*>(r1 + tx.i0 * C + c);
+                        const float4 d = *reinterpret_cast<const float4*>(r1 + tx.i1 * C + c);
+                        f[c][p] = bilerp(ty, tx, a.x, bq.x, cq.x, d.x);
+                        f[c + 1][p] = bilerp(ty, tx, a.y, bq.y, cq.y, d.y);
+                        f[c + 2][p] = bilerp(ty, tx, a.z, bq.z, cq.z, d.z);
+                        f[c + 3][p] = bilerp(ty, tx, a.w, bq.w, cq.w, d.w);
                     }
                 }
             } else {
 #pragma unroll
                 for (int c = 0; c < CM; ++c) {
                     if (c < C)
-                        f[c][p] = ly0 * (lx0 * r0[x0 * C + c] + lx1 * r0[x1 * C + c]) +
-                                  ly1 * (lx0 * r1[x0 * C + c] + lx1 * r1[x1 * C + c]);
+                        f[c][p] = bilerp(ty, tx, r0[tx.i0 * C + c], r0[tx.i1 * C + c], r1[tx.i0 * C + c], r1[tx.i1 * C + c]);
                 }
             }
         }
         const int64_t pix = (int64_t)Y * W + xg * PX;
         store_feats<PX, CM>(f, C, feats, (int64_t)b * HW + pix);
         dist_and_store<PX, CM>(f, sp, C, K, logits, argmax, dissum, HW, pix, (int64_t)b * K * HW, (int64_t)b * HW);
+    }
+}
+
+// ---- merged prediction of the incremental multi-head model (test_self_distillation.py:292-297 of the reference) straight
+// from the heads' low-resolution embeddings: no full-resolution logits or features exist.  With the prototypes 3 I_K
+// (network/utils.py:103-106; a K = C + 1 head's last row, cut to the C carried channels, is zero)
+//     -d_k = sum_c (f_c - 3 delta_kc)^2 = S + 9 - 6 f_k,  S = sum_c f_c^2 the same for every k    (k < C)
+//     -d_C = S = S + 9 - 6 * 1.5
+// so the first maximal d_k is the first maximal f_k over k < K, with 1.5 standing in for f_C.  The kernel compares the
+// interpolated f_k themselves: K channels per tap instead of C, no S (whose rounding would only create ties), and exact
+// ties of f stay exact ties of d.
+struct PredictArgs {
+    DmlPredictHead head[DML_PREDICT_MAX_HEADS];
+    int n;
+    unsigned vec;      // bit i: head i's rows can be read as 16-byte vectors
+};
+
+__device__ __forceinline__ int head_first_max(const DmlPredictHead& hd, bool vec, int b, const Tap& ty, const Tap& tx,
+                                              int h, int w) {
+    const int64_t ld = hd.ld;
+    const float* r0 = hd.e + ((int64_t)b * h + ty.i0) * w * ld;
+    const float* r1 = hd.e + ((int64_t)b * h + ty.i1) * w * ld;
+    const float* p00 = r0 + tx.i0 * ld;
+    const float* p01 = r0 + tx.i1 * ld;
+    const float* p10 = r1 + tx.i0 * ld;
+    const float* p11 = r1 + tx.i1 * ld;
+    const int Kc = min(hd.K, hd.C);
+    float best = -INFINITY;
+    int bi = 0;
+    if (vec) {
+        for (int c = 0; c < Kc; c += 4) {              // (vec: C % 4 == 0, so c + 3 < C)
+            const float4 a = *reinterpret_cast<const float4*>(p00 + c);
+            const float4 bq = *reinterpret_cast<const float4*>(p01 + c);
+            const float4 cq = *reinterpret_cast<const float4*>(p10 + c);
+            const float4 d = *reinterpret_cast<const float4*>(p11 + c);
+            const float v[4] = {bilerp(ty, tx, a.x, bq.x, cq.x, d.x), bilerp(ty, tx, a.y, bq.y, cq.y, d.y),
+                                bilerp(ty, tx, a.z, bq.z, cq.z, d.z), bilerp(ty, tx, a.w, bq.w, cq.w, d.w)};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c + j < Kc && v[j] > best) { best = v[j]; bi = c + j; }
+        }
+    } else {
+        for (int c = 0; c < Kc; ++c) {
+            const float v = bilerp(ty, tx, p00[c], p01[c], p10[c], p11[c]);
+            if (v > best) { best = v; bi = c; }
+        }
+    }
+    if (hd.K > hd.C && 1.5f > best) bi = hd.C;
+    return bi;
+}
+
+// One lane owns two consecutive pixels of the flat [B H W] index space = one 16-byte store of preds.  `off` (0 / 1) shifts
+// the pairs so that they start on a 16-byte boundary of preds: pair g is pixels 2 g - off, 2 g - off + 1, and a pair
+// with only one pixel inside [0, total) -- the first one of a misaligned buffer, the last one of an odd count -- stores
+// that pixel alone.
+__global__ __launch_bounds__(256) void incremental_predict_kernel(const PredictArgs args, int64_t* __restrict__ preds,
+                                                                  uint8_t* __restrict__ head_argmax, int B, int h,
+                                                                  int w, int H, int W, float sy, float sx, int off) {
+    const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW, pairs = (total + off + 1) / 2;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < pairs; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t first = 2 * g - off;
+        // (b, Y, X) of the pair's first pixel inside the range; its neighbour follows by carry
+        int64_t cur = first < 0 ? 0 : first;
+        int b, Y, X;
+        if (total <= 0x7fffffffll) {
+            const unsigned u = (unsigned)cur, hw = (unsigned)HW;
+            b = (int)(u / hw);
+            const unsigned r = u - (unsigned)b * hw;
+            Y = (int)(r / (unsigned)W);
+            X = (int)(r - (unsigned)Y * (unsigned)W);
+        } else {
+            b = (int)(cur / HW);
+            const int64_t r = cur - (int64_t)b * HW;
+            Y = (int)(r / W);
+            X = (int)(r - (int64_t)Y * W);
+        }
+        int64_t res[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int64_t pix = first + p;
+            res[p] = 0;
+            if (pix < 0 || pix >= total) continue;
+            if (pix != cur) {
+                cur = pix;
+                if (++X == W) { X = 0; if (++Y == H) { Y = 0; ++b; } }
+            }
+            const Tap ty = src_tap(sy, Y, h), tx = src_tap(sx, X, w);
+            int pred = 0;
+            for (int i = 0; i < args.n; ++i) {
+                const int am = head_first_max(args.head[i], (args.vec >> i) & 1u, b, ty, tx, h, w);
+                if (head_argmax != nullptr) head_argmax[(int64_t)i * total + pix] = (uint8_t)am;
+                if (i == 0 || am == args.head[i].novel_id) pred = am;      // a later head overrides an earlier one
+            }
+            res[p] = pred;
+        }
+        if (first >= 0 && first + 1 < total) {
+            typedef long long i64x2 __attribute__((ext_vector_type(2)));
+            const i64x2 v = {(long long)res[0], (long long)res[1]};
+            *reinterpret_cast<i64x2*>(preds + first) = v;
+        } else {
+            if (first >= 0 && first < total) preds[first] = res[0];
+            if (first + 1 >= 0 && first + 1 < total) preds[first + 1] = res[1];
+        }
     }
 }
 
@@ -1358,6 +1464,29 @@ extern "C" int dml_upsample_dist_fwd(const float* e, const float* protos, float*
         else hipLaunchKernelGGL((upsample_dist_fwd_kernel<1, 32>), dim3(grid), dim3(256), 0, st, e, protos, logits, feats,
                            argmax, dissum, B, h, w, C, K, H, W, sy, sx);
     }
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dml_incremental_predict(const DmlPredictHead* heads, int n, int64_t* preds, uint8_t* head_argmax,
+                                       int B, int h, int w, int H, int W, void* stream) {
+    if (!heads || !preds || n < 1 || B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DML_EINVAL;
+    if (n > DML_PREDICT_MAX_HEADS) return DML_EUNSUPPORTED;
+    PredictArgs args = {};
+    args.n = n;
+    for (int i = 0; i < n; ++i) {
+        const DmlPredictHead& hd = heads[i];
+        if (!hd.e || hd.C <= 0 || hd.K <= 0 || hd.ld < hd.C) return DML_EINVAL;
+        if (hd.C > MAXC || hd.K > MAXK || hd.K > hd.C + 1) return DML_EUNSUPPORTED;
+        args.head[i] = hd;
+        if ((hd.C & 3) == 0 && (hd.ld & 3) == 0 && (reinterpret_cast<uintptr_t>(hd.e) & 15) == 0) args.vec |= 1u << i;
+    }
+    if ((reinterpret_cast<uintptr_t>(preds) & 7) != 0) return DML_EALIGN;
+    const int off = (int)((reinterpret_cast<uintptr_t>(preds) >> 3) & 1);
+    const int64_t pairs = ((int64_t)B * H * W + off + 1) / 2;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    hipLaunchKernelGGL(incremental_predict_kernel, dim3(grid_for(pairs, 256, 256 * 16)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), args, preds, head_argmax, B, h, w, H, W, sy, sx, off);
     DML_LAUNCH_CHECK();
     return 0;
 }

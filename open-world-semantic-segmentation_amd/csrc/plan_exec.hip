@@ -92,6 +92,7 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_bilinear_bwd),
     DML_ENTRY(dml_proto_dist_fwd),
     DML_ENTRY(dml_upsample_dist_fwd),
+    DML_ENTRY(dml_incremental_predict),
     DML_ENTRY(dml_proto_dist_bwd),
     DML_ENTRY(dml_head_bwd_fused),
     DML_ENTRY(dml_argmax_msp),

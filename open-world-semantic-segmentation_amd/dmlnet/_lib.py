@@ -108,6 +108,14 @@ class ResizeScale(C.Structure):
 RESIZE_MAX_SCALES = 8
 
 
+class PredictHead(C.Structure):
+    """DmlPredictHead: one head of a dml_incremental_predict launch (host array; `e` is a device pointer)"""
+    _fields_ = [("e", c_p), ("C", C.c_int32), ("K", C.c_int32), ("ld", C.c_int32), ("novel_id", C.c_int32)]
+
+
+PREDICT_MAX_HEADS = 4
+
+
 class ScaleWindow(C.Structure):
     """DmlScaleWindow: one sample of a dml_aug_scale_window launch (element offsets into the batch's table buffer)"""
     _fields_ = [("hbounds", C.c_int32), ("hcoef", C.c_int32), ("vbounds", C.c_int32), ("vcoef", C.c_int32),
@@ -167,6 +175,7 @@ _PROTOS = {
     "dml_bilinear_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_proto_dist_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_upsample_dist_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "dml_incremental_predict": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_proto_dist_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_head_bwd_fused": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_i, c_p]),
     "dml_argmax_msp": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

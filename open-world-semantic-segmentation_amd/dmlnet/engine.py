@@ -324,8 +324,13 @@ class ConvUnit:
 
 
 class Plan:
-    def __init__(self, engine: "Engine", B: int, H: int, W: int, dtype: torch.dtype, training: bool):
+    def __init__(self, engine: "Engine", B: int, H: int, W: int, dtype: torch.dtype, training: bool, predict_heads=None):
         self.e = engine
+        # prediction plan (Engine.predict): the first `predict_heads` heads up to their final 1x1 convolution, then ONE
+        # dml_incremental_predict over their low-resolution embeddings instead of a dml_upsample_dist_fwd per head
+        self.predict_heads = predict_heads
+        if predict_heads is not None and training:
+            raise ValueError("a prediction plan is an inference plan")
         self.lib = engine.lib
         self.B, self.H, self.W = B, H, W
         self.dtype, self.dt = dtype, _dt(dtype)
@@ -1131,6 +1136,8 @@ class Plan:
         lib, m, st = self.lib, self.e.model, self.e.store
         B, H, W = self.B, self.H, self.W
         bb, head_modules = m.backbone, self.e.head_modules()
+        if self.predict_heads is not None:
+            head_modules = head_modules[:self.predict_heads]
         self.pre_prep = []
         n_fixed = 0
         for mod in itertools.chain(bb.modules(), *[h.modules() for h in head_modules]):
@@ -1203,6 +1210,14 @@ class Plan:
             self.h2_bound_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
             self.h2_bound_args[0], self.h2_bound_args[1] = self.h2_bound_table.data_ptr(), len(self.h2_bound_tab)
         self.K, self.Kp = self.heads[0].K, self.heads[0].Kp
+        if self.predict_heads is not None:
+            # head i > 0 contributes its own last prototype, class K_i - 1 (16 + (i - 1) for the reference's head widths,
+            # test_self_distillation.py:295-297)
+            tab = (_lib.PredictHead * len(self.heads))(*[
+                _lib.PredictHead(rec.emb.ptr, rec.Kp, rec.K, rec.emb.ld, rec.K - 1) for rec in self.heads])
+            self.keep.append(tab)
+            self.predict_args = self.call(self.fwd, lib.dml_incremental_predict, C.addressof(tab), len(self.heads), 0, None,
+                                          B, self.heads[0].emb.H, self.heads[0].emb.W, H, W)
         self.nbt_inc = None
         if self.training and n_fixed:
             self.nbt_inc = torch.tensor([1 if mod.training else 0 for mod in st.bn_modules], dtype=torch.int64,
@@ -1363,8 +1378,11 @@ class Plan:
         self.conv_fwd(ucls.z, fin, emb, w_fin, None, bias_ptr=fin_bias_ptr, N=Kp)
         protos = self.e.prototypes_padded(K, Kp)
         # fused final upsample + distance head (network/utils.py:88-118); outputs are per-call tensors
-        head_args = self.call(self.fwd, lib.dml_upsample_dist_fwd, emb.ptr, protos.data_ptr(), 0, 0,
-                                   None, None, B, emb.H, emb.W, Kp, K, H, W)
+        # (a prediction plan stops at the embedding: Plan.build appends one launch for all heads)
+        head_args = None
+        if self.predict_heads is None:
+            head_args = self.call(self.fwd, lib.dml_upsample_dist_fwd, emb.ptr, protos.data_ptr(), 0, 0,
+                                       None, None, B, emb.H, emb.W, Kp, K, H, W)
         rec = HeadRec()
         rec.K, rec.Kp, rec.emb, rec.protos, rec.head_args = K, Kp, emb, protos, head_args
         rec.cat1, rec.cat2, rec.up_low, rec.branches, rec.pooled, rec.upool = cat1, cat2, up_low, branches, pooled, upool
@@ -1797,18 +1815,49 @@ class Engine:
                 sig |= 1 << i
         return sig
 
-    def plan_for(self, x: torch.Tensor, dtype: torch.dtype, training: bool) -> Plan:
+    def plan_for(self, x: torch.Tensor, dtype: torch.dtype, training: bool, predict_heads=None) -> Plan:
         if not self.store.is_bound(x.device):
             self.store.bind(x.device)
             self.plans.clear()
             self._protos.clear()
         B, Cin, H, W = x.shape
         key = (B, H, W, dtype, training, bool(self.sync_bn), self.bn_modes() if training else 0, int(self.f32_split))
+        if predict_heads is not None:
+            # a plan of its own: the inference plan behind model(x) keeps its launch list, buffers and results
+            key += ("predict", int(predict_heads))
         plan = self.plans.get(key)
         if plan is None:
-            plan = self.plan_cls(self, B, H, W, dtype, training)
+            if predict_heads is not None:
+                plan = self.plan_cls(self, B, H, W, dtype, training, predict_heads=int(predict_heads))
+            else:
+                plan = self.plan_cls(self, B, H, W, dtype, training)
             self.plans[key] = plan
         return plan
+
+    def predict(self, x: torch.Tensor, dtype: torch.dtype, n_heads: int) -> torch.Tensor:
+        """Merged prediction [B,H,W] int64 of heads 0 .. n_heads-1 (test_self_distillation.py:292-297 of the reference; one
+        head: its argmax) through the prediction plan: no logits or features at full resolution."""
+        if not x.is_cuda:
+            raise RuntimeError("DMLNet HIP engine needs a ROCm device tensor (got %s); the CPU restatement lives "
+                               "in oracle/ and is test infrastructure only" % x.device)
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("expected input [B,3,H,W], got %s" % (tuple(x.shape),))
+        if not 1 <= n_heads <= min(len(self.head_modules()), _lib.PREDICT_MAX_HEADS):
+            raise ValueError("predict over %d heads: the model has %d, one launch merges at most %d"
+                             % (n_heads, len(self.head_modules()), _lib.PREDICT_MAX_HEADS))
+        x = x.contiguous().float()
+        plan = self.plan_for(x, dtype, False, predict_heads=n_heads)
+        if getattr(plan, "predict_args", None) is None:
+            raise NotImplementedError("%s has no prediction plan" % type(plan).__name__)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        plan.refresh_weights(stream, overlap=False)
+        B, _, H, W = x.shape
+        preds = torch.empty((B, H, W), dtype=torch.int64, device=x.device)
+        plan.predict_args[2] = preds.data_ptr()
+        plan.images_args[0] = x.data_ptr()
+        plan.run_forward(stream)
+        plan.last_input = x
+        return preds
 
     def forward(self, x: torch.Tensor, dtype: torch.dtype, training: bool):
         if not x.is_cuda:

@@ -185,6 +185,17 @@ class DeepLabV3_embedding(nn.Module):
             logits, feats = logits[0], feats[0]
         return logits, eng.prototypes(k), feats
 
+    def _predict(self, x, n_heads):
+        if self.training:
+            raise RuntimeError("predict() is an evaluation step: call model.eval() first")
+        with torch.no_grad():
+            return self._engine.predict(x, self.compute_dtype, n_heads)
+
+    def predict(self, x):
+        """argmax_k of forward(x)[0] as [B,H,W] int64, from the low-resolution embedding in one pass: the logits and features
+        of forward() are never written (eval mode only)."""
+        return self._predict(x, 1)
+
 
 class DeepLabV3_embedding_self_distillation(DeepLabV3_embedding):
     """network/_deeplab.py:45 + network/utils.py:120-193 of the reference: one backbone, a base head with 16 prototypes
@@ -195,8 +206,13 @@ class DeepLabV3_embedding_self_distillation(DeepLabV3_embedding):
     base_classes = 16            # utils.py:131 hard-codes it
     cls_novel = 1                # utils.py:125
 
-    def __init__(self, backbone, rates):
+    def __init__(self, backbone, rates, cls_novel=None):
         nn.Module.__init__(self)
+        if cls_novel is not None:
+            # a 16+2 / 16+3 checkpoint: heads of 17, 18, 19 under the reference's keys classifier_1, classifier_2, classifier_3
+            if int(cls_novel) < 0:
+                raise ValueError("cls_novel must be >= 0")
+            self.cls_novel = int(cls_novel)
         self.backbone = backbone
         self.classifier_list = ["classifier"] + ["classifier_%d" % (i + 1) for i in range(self.cls_novel)]
         self.classifier = DeepLabHeadV3Plus(2048, 256, self.base_classes, rates)
@@ -224,8 +240,21 @@ class DeepLabV3_embedding_self_distillation(DeepLabV3_embedding):
         centers = [eng.prototypes(h.classifier[3].out_channels) for h in self.head_modules()]
         return logits, centers, feats
 
+    def predict(self, x, novel_cls=None):
+        """The merged prediction of the reference's evaluation (test_self_distillation.py:292-297) as [B,H,W] int64: the base
+        head's argmax, then for i = 1 .. novel_cls in order every pixel where head i's argmax is ITS novel class
+        (base_classes + i - 1) takes that class.  novel_cls defaults to every further head; a smaller value uses heads
+        0 .. novel_cls only (the reference's range(opts.novel_cls)); 0 is the base head's argmax.  One pass over the heads'
+        low-resolution embeddings: forward()'s logits and features are never written (eval mode only)."""
+        n_further = len(self.classifier_list) - 1
+        if novel_cls is None:
+            novel_cls = n_further
+        if not 0 <= int(novel_cls) <= n_further:
+            raise ValueError("novel_cls=%r: the model has %d further head(s)" % (novel_cls, n_further))
+        return self._predict(x, int(novel_cls) + 1)
 
-def _segm_resnet(name, backbone_name, num_classes, output_stride, pretrained_backbone):
+
+def _segm_resnet(name, backbone_name, num_classes, output_stride, pretrained_backbone, cls_novel=None):
     if pretrained_backbone:
         # resnet.py:216 downloads ImageNet weights; load them yourself with load_state_dict instead
         import warnings
@@ -238,7 +267,7 @@ def _segm_resnet(name, backbone_name, num_classes, output_stride, pretrained_bac
         raise NotImplementedError(backbone_name)
     backbone = ResNetTrunk(_DEPTHS[backbone_name], dilate)
     if name == "deeplabv3plus_embedding_self_distillation":
-        return DeepLabV3_embedding_self_distillation(backbone, rates)        # modeling.py:39-40: num_classes unused
+        return DeepLabV3_embedding_self_distillation(backbone, rates, cls_novel=cls_novel)   # modeling.py:39-40: num_classes unused
     if name != "deeplabv3plus_embedding":
         raise NotImplementedError("%s: only the embedding DeepLabV3+ models are built on MI355X (BASELINE.json)" % name)
     return DeepLabV3_embedding(backbone, DeepLabHeadV3Plus(2048, 256, num_classes, rates))
