@@ -345,7 +345,7 @@ int dml_bn_bwd_reduce(const void* dz, const void* y, const void* z, const uint8_
  * coef[4][N] with dy = coef0*g + coef1*(y - coef3) + coef2  (coef3 = batch mean).
  * M = 0 selects a layer that normalised with FIXED statistics (BatchNorm2d.eval() inside a training step, the
  * reference's main_self_distillation.py:432-435): save_mean / save_invstd are then the running statistics, the two
- * correction terms are zero (coef1 = coef2 = 0) and dgamma / dbeta are unchanged.
+ * correction terms are zero (coef1 = coef2 = 0); dgamma / dbeta still receive the sums (+=), as autograd of an eval() BatchNorm gives.
  * With more than 2048 partial rows they are first folded in place (two coalesced stages): `partials` is clobbered. */
 int dml_bn_bwd_finalize(float* partials, int nblocks, int64_t M, int N, const float* gamma,
                         const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
