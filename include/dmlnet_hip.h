@@ -519,6 +519,22 @@ int dml_novel_relabel_multi(const float* feats, const float* logits, const float
                             int64_t* preds, int B, int C, int K, int H, int W, int N, float thresh, int vs_known,
                             void* stream);
 
+/* kNN cosine-similarity anomaly score (anomaly/eval_ood_traditional.py:511-530 of the reference, `--ood knn`, neighbor_size = 9
+ * there) of feats[B,C,H,W] fp32 (NCHW, contiguous: the multi-scale mean of the upsampled embedding) in one launch:
+ *   n(b,y,x) = f(b,:,y,x) / max(|f(b,:,y,x)|_2, 1e-8)      (ATen's cosine_similarity: each norm clamped on its own)
+ *   score[b,y,x] = sum_{i=1..R} sum_{j=1..R} n(b,y,x) . n(b,y+i,x+j) + n(b,y,x) . n(b,y-i,x-j),   R = neighbor_size - 1
+ * -- the down-right and the up-left quadrant only, 2 R^2 neighbours, none on the pixel's own row or column; a neighbour outside
+ * the image contributes exactly 0 (the reference's shifted copy is zero there), so images smaller than the neighbourhood are
+ * fine; a pixel whose own vector is zero scores exactly 0; neighbor_size = 1 gives an all-zero map.  Computed as
+ * sum_c n_c(p) * (row sums, then column sums of n_c over the quadrants): 4 R additions per pixel and channel.  No workspace, no
+ * atomics, every sum in a fixed order over the plain values: bitwise reproducible, image b of a batch equals the image alone, and
+ * C = 1 gives exact integers.  Inputs |f| <= 1e18 (the squares stay finite).  16-byte loads and stores when W % 4 == 0 and both
+ * pointers are 16-byte aligned, one float per lane otherwise.  The reference's resize of the map to segSize is the identity
+ * (feats already has that size) and its plot is not reproduced.
+ * DML_EINVAL: a NULL pointer, B, C, H, W <= 0 or neighbor_size < 1.  DML_EUNSUPPORTED: C > 32, neighbor_size > 17, B > 65535 or
+ * B H W > 2^40.  Nothing is launched when a code is returned. */
+int dml_knn_cosine_score(const float* feats, float* score, int B, int C, int H, int W, int neighbor_size, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DML loss = CE(-dist^2)/n + alpha * VAR/n (anomaly/models/models.py:42-78; live part of
  * utils/loss.py:34-42 is alpha = 0).

@@ -4,9 +4,13 @@
 
 Per frame: the resized copies go through `models.evaluate_multiscale` (the loop of :198-210, mean folded into the
 upsample kernel, scales concurrent), `pred = argmax` (:218), the confidence map of `--ood`
-(:275-340: msp | maxlogit | dissum | background; the CRF / kNN variants of the reference need pydensecrf / are
-plotting experiments and are not offered), then `eval_ood_measure` (:128-148) and the pixel accuracy / IoU meters
-(:548-556) -- all on the device; nothing but the three OOD numbers and the confusion counts per frame reaches the host.
+(:275-340: msp | maxlogit | dissum | background, and :511-530: knn -- the sum, over the 8 x 8 pixels down-right and the
+8 x 8 pixels up-left of each pixel, of the cosine similarity between its embedding `ft1` and theirs, 0 beyond the image
+border: the reference's 128 rounds of zero-filled shifted copies in one kernel, utils.knn_cosine_score; its plt.figure /
+imshow / show calls and its resize of the map to segSize, the identity on a map that already has that size, are not
+reproduced; the two CRF variants of the reference need pydensecrf and are not offered), then `eval_ood_measure`
+(:128-148) and the pixel accuracy / IoU meters (:548-556) -- all on the device; nothing but the three OOD numbers and
+the confusion counts per frame reaches the host.
 Data: a StreetHazards-layout tree from disk (the reference's command line: `--cfg FILE`, `--gpu`, `--ood`,
 `--exclude_back` and trailing `KEY VALUE` overrides; datasets/streethazards.py decodes on host threads and resizes /
 normalises on the device, bit for bit the reference's ValDataset tensors), or `--synthetic` frames.
@@ -34,8 +38,13 @@ def resized_shapes(h, w):
     return shapes(h, w, IMG_SIZES, IMG_MAX_SIZE, PADDING_CONSTANT)
 
 
-def confidence(scores, ood, exclude_back=False):
-    """:275-340.  scores [1, K, H, W] on the device -> conf [H, W] on the device."""
+def confidence(scores, ood, exclude_back=False, feats=None):
+    """:275-340, :511-530.  scores [1, K, H, W] on the device -> conf [H, W] on the device.  `knn` reads the embedding
+    feats [1, C, H, W] instead of the scores (the reference's `ft1`), so --exclude_back does not touch it."""
+    if ood == "knn":
+        if feats is None:
+            raise ValueError("--ood knn scores the embedding: pass feats")
+        return utils.knn_cosine_score(feats)[0]
     tmp = scores[:, 1:].contiguous() if exclude_back else scores
     if ood == "msp":
         return utils.argmax_msp(tmp)[1][0]
@@ -61,7 +70,7 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
         scores, ft1 = models.evaluate_multiscale(segmentation_module, imgs, seg_size)
         known = scores.shape[1]
         pred = utils.argmax_msp(scores)[0]
-        conf = confidence(scores, ood, exclude_back)
+        conf = confidence(scores, ood, exclude_back, feats=ft1)
         res = anom_utils.eval_ood_measure(conf, seg_label, out_labels)
         if res is not None:
             aurocs.append(res[0]); auprs.append(res[1]); fprs.append(res[2])
@@ -134,7 +143,7 @@ def load_cfg(cfg_file, overrides):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--ood", default="dissum", choices=["msp", "maxlogit", "dissum", "background"])
+    p.add_argument("--ood", default="dissum", choices=["msp", "maxlogit", "dissum", "background", "knn"])
     p.add_argument("--exclude_back", action="store_true")
     p.add_argument("--out_label", type=int, default=13, help="cfg.OOD.out_labels: the anomaly id of StreetHazards")
     p.add_argument("--num_images", type=int, default=4)

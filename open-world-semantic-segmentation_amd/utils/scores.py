@@ -1,5 +1,5 @@
 """Open-world scores computed on the device instead of on 134 MB/img host copies
-(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305)."""
+(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305,511-530)."""
 from __future__ import annotations
 
 import numpy as np
@@ -41,6 +41,23 @@ def dissum_score(logits: torch.Tensor, clip: float = 1000.0, inclusive: bool = F
     work = torch.empty(2 * B, dtype=torch.float32, device=logits.device)
     _lib.check(lib.dml_dissum_score(logits.data_ptr(), score.data_ptr(), work.data_ptr(), B, K, H, W, float(clip),
                                     1 if inclusive else 0, _st(logits)), "dml_dissum_score")
+    return score
+
+
+def knn_cosine_score(feats: torch.Tensor, neighbor_size: int = 9) -> torch.Tensor:
+    """The kNN anomaly score of anomaly/eval_ood_traditional.py:511-530 on feats [B, C, H, W] (the second return value of
+    models.evaluate_multiscale): per pixel the sum of the cosine similarities with the (neighbor_size - 1)^2 pixels
+    down-right and the (neighbor_size - 1)^2 pixels up-left of it, 0 for a neighbour outside the image
+    (dml_knn_cosine_score) -> [B, H, W]."""
+    _need_cuda(feats)
+    if feats.dim() != 4:
+        raise ValueError("feats must be [B, C, H, W]")
+    lib = _lib.load()
+    feats = feats.contiguous().float()
+    B, C, H, W = feats.shape
+    score = torch.empty((B, H, W), dtype=torch.float32, device=feats.device)
+    _lib.check(lib.dml_knn_cosine_score(feats.data_ptr(), score.data_ptr(), B, C, H, W, int(neighbor_size), _st(feats)),
+               "dml_knn_cosine_score")
     return score
 
 
