@@ -357,6 +357,40 @@ int dml_bn_bwd_apply(const void* dz, const void* y, const void* z, const uint8_t
                      void* dres, int64_t M, int N, int lddz, int ldy, int ldz, int lddy, int lddres,
                      int relu, float gscale, int dres_accum, int dtype, float* amax, void* planes, int64_t plane_stride,
                      int32_t ldp, const float* unscale, void* stream);
+/* The stem (network/backbone/resnet.py:139-143: conv1 -> bn1 -> ReLU -> MaxPool2d(3, 2, 1)) without its full-resolution tensors.
+ * Forward: dml_bn_apply (ReLU) + dml_maxpool3x3s2_fwd in one pass over y[B][H][W] (pitch ldy, fp32, C % 8 == 0): per pooled
+ * element the window taps in the order r, then s, z = (y - mean) * scale + shift, ReLU, the maximum with dml_maxpool3x3s2_fwd's
+ * rule (first wins on ties, NaN propagates) -- `p` and `argmax` are bit-equal to the two-call sequence's.  Outputs, each optional
+ * (one of p / planes is required): p[B][Ho][Wo][C] fp32; argmax (one byte per element, 0 .. 8); `mask`, the ReLU mask of the
+ * UNPOOLED tensor in dml_bn_apply's fp32 layout (one byte per four channels, [B H W][C / 4]); the two fp16 planes of p (pitch C,
+ * lo `plane_stride` elements behind hi) scaled by 1 / unscale[0] -- the BatchNorm's bound (dml_h2_bound_bn) holds for the pooled
+ * tensor too, a maximum of bounded values; `amax`, 1024 zeroed words raised to max |p| as dml_bn_apply raises them, for a
+ * dml_h2_split of p with amax_known = 1 (the scale, and with it the planes, that the split computes from p on its own). */
+int dml_bn_relu_maxpool3x3s2_fwd(const void* y, const float* scale, const float* shift, const float* mean, void* p,
+                                 uint8_t* argmax, uint8_t* mask, void* planes, int64_t plane_stride, const float* unscale,
+                                 float* amax, int B, int H, int W, int C, int ldy, void* stream);
+/* Backward: dml_maxpool3x3s2_bwd + dml_bn_bwd_reduce / dml_bn_bwd_apply (ReLU from `mask`, gscale 1) without the d(z) tensor
+ * between them.  Both form g of an input pixel from dp = d(p)[B][Ho][Wo][C] and the argmax bytes -- its (at most four) windows added
+ * in dml_maxpool3x3s2_bwd's order, then the pixel's mask bits -- so g, and with equal `coef` dy, are bit-equal to the three-call
+ * sequence's.  fp32, C % 4 == 0.  The reduce walks the pixels in dml_bn_bwd_reduce's geometry and order: *nblocks and the partial
+ * rows (for dml_bn_bwd_finalize[_bound]; `gmax` as there) are bit-equal to what that call writes from the d(z) tensor; the apply writes dy[B H W] (pitch lddy) and / or its planes as dml_bn_bwd_apply does. */
+int dml_stem_bn_bwd_reduce(const void* dp, const uint8_t* argmax, const uint8_t* mask, const void* y, const float* save_mean,
+                           const float* save_invstd, float* partials, int B, int H, int W, int C, int ldy, int* nblocks,
+                           float* gmax, void* stream);
+int dml_stem_bn_bwd_apply(const void* dp, const uint8_t* argmax, const uint8_t* mask, const void* y, const float* coef, void* dy,
+                          int B, int H, int W, int C, int ldy, int lddy, void* planes, int64_t plane_stride, int32_t ldp,
+                          const float* unscale, void* stream);
+/* The BatchNorm backward of the unit in FRONT of a 1x1 convolution with few output channels (the decoder's 256 -> 16 embedding
+ * conv, network/utils.py:24-27), without that conv's data gradient as a tensor: dz[m][c] = sum_{k < K} de[m][k] w[k][c], formed per
+ * row in registers with fp32 FMAs in the order k = 0, 1, ... (de[M][Kp] with pitch ldde, Kp in {8, 16, 24, 32} columns of which the
+ * first K count; w[K][N] with pitch ldw: the convolution's own weight).  Otherwise dml_bn_bwd_reduce / dml_bn_bwd_apply for fp32
+ * tensors with the ReLU taken from `mask` and gscale 1. */
+int dml_head_bn_bwd_reduce(const void* de, const float* w, const void* y, const uint8_t* mask, const float* save_mean,
+                           const float* save_invstd, float* partials, int64_t M, int N, int K, int Kp, int ldde, int ldw, int ldy,
+                           int relu, int* nblocks, float* gmax, void* stream);
+int dml_head_bn_bwd_apply(const void* de, const float* w, const void* y, const uint8_t* mask, const float* coef, void* dy,
+                          int64_t M, int N, int K, int Kp, int ldde, int ldw, int ldy, int lddy, int relu, void* planes,
+                          int64_t plane_stride, int32_t ldp, const float* unscale, void* stream);
 /* Scale of a batch-statistics BatchNorm output's fp16 planes from a BOUND on its magnitude, available before the tensor is
  * written: every normalised element obeys |y - mean| * invstd <= sqrt(count) (count = elements per channel over all ranks that
  * share the statistics), so |z| <= max_c (|gamma_c| sqrt(count) + |beta_c|) * mult + max |res| (`mult`: 1, or the dropout's

@@ -1195,6 +1195,639 @@ extern "C" int dml_bn_bwd_apply(const void* dz, const void* y, const void* z, co
     return 0;
 }
 
+// ---- the stem: BatchNorm + ReLU + 3x3 / stride 2 / pad 1 max pool without the full-resolution tensors between them ------------
+// dml_bn_apply wrote z0 = relu(bn(y)) (604 MB at 16 x 384 x 384 x 64) for dml_maxpool3x3s2_fwd to read once, and the backward
+// scattered d(p0) into a d(z0) of the same size for the two BatchNorm-backward passes to read once each.  Here the forward forms z
+// per window tap and keeps the maximum; the backward passes gather a pixel's gradient from its (at most four) windows themselves.
+namespace {
+// One thread per pooled pixel and EIGHT channels (fp32): taps in the order r, then s, z exactly as bn_apply_cols_kernel forms it, the
+// comparison of maxpool_fwd_kernel (first wins on ties, NaN propagates).  The thread also OWNS the 2 x 2 input pixels (2 yo + {0, 1},
+// 2 xo + {0, 1}) -- taps r, s in {1, 2} of its window, every input pixel belongs to exactly one thread -- and writes their ReLU mask
+// bytes (one per four channels, dml_bn_apply's layout).  The pooled tensor leaves as fp32 and / or as the two fp16 planes.
+__global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(
+    const float* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
+    float* __restrict__ p, uint8_t* __restrict__ argmax, uint8_t* __restrict__ mask, _Float16* __restrict__ planes,
+    int64_t plane_stride, const float* __restrict__ unscale, uint32_t* __restrict__ amax, int B, int H, int W, int C, int ldy,
+    int Ho, int Wo) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    constexpr int V = 8;
+    const int CV = C / V;
+    const int64_t total = (int64_t)B * Ho * Wo * CV;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = i < total;                  // (idle threads stay for the wave reduction of amax at the end)
+    if (!act && amax == nullptr) return;
+    if (!act) i = 0;
+    uint32_t amx = 0;                            // largest pooled value this thread stores (dml_h2_split with amax_known)
+    const int cv = (int)(i % CV);
+    int64_t pix = i / CV;
+    const int xo = (int)(pix % Wo); pix /= Wo;
+    const int yo = (int)(pix % Ho);
+    const int b = (int)(pix / Ho);
+    const int c = cv * V;
+    float sc[V], sh[V], mu[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) { sc[q] = scale[c + q]; sh[q] = shift[c + q]; mu[q] = mean[c + q]; }
+    float best[V];
+    int idx[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) { best[q] = -INFINITY; idx[q] = -1; }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int yi = yo * 2 - 1 + r;
+        if ((unsigned)yi >= (unsigned)H) continue;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int xi = xo * 2 - 1 + s;
+            if ((unsigned)xi >= (unsigned)W) continue;
+            const int64_t m = ((int64_t)b * H + yi) * W + xi;
+            const float4 va = *reinterpret_cast<const float4*>(y + m * ldy + c);
+            const float4 vb = *reinterpret_cast<const float4*>(y + m * ldy + c + 4);
+            float v[V] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                v[q] = (v[q] - mu[q]) * sc[q] + sh[q];
+                v[q] = v[q] > 0.f ? v[q] : 0.f;
+            }
+            if (r >= 1 && s >= 1 && mask != nullptr && act) {
+                uint32_t bits = 0;
+#pragma unroll
+                for (int q = 0; q < V; ++q) bits |= (v[q] > 0.f ? 1u : 0u) << (q + (q >= 4 ? 4 : 0));
+                *reinterpret_cast<uint16_t*>(mask + m * (C / 4) + cv * 2) = (uint16_t)bits;
+            }
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                if (idx[q] < 0 || v[q] > best[q] || v[q] != v[q]) { best[q] = v[q]; idx[q] = r * 3 + s; }
+            }
+        }
+    }
+    const int64_t o = (((int64_t)b * Ho + yo) * Wo + xo) * C + c;
+    if (amax != nullptr) {
+#pragma unroll
+        for (int q = 0; q < V; ++q) amx = max(amx, __float_as_uint(best[q]) & 0x7fffffffu);
+        amax_publish(act ? amx : 0u, amax);
+        if (!act) return;
+    }
+    if (p != nullptr) {
+        *reinterpret_cast<float4*>(p + o) = make_float4(best[0], best[1], best[2], best[3]);
+        *reinterpret_cast<float4*>(p + o + 4) = make_float4(best[4], best[5], best[6], best[7]);
+    }
+    if (argmax != nullptr) {
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int q = 0; q < V; ++q) w[q >> 2] |= ((uint32_t)idx[q] & 0xffu) << ((q & 3) * 8);
+        *reinterpret_cast<uint2*>(argmax + o) = make_uint2(w[0], w[1]);
+    }
+    if (planes != nullptr) {
+        const float h2s = 1.0f / unscale[0];      // exact: a power of two
+        h8 hi, lo;
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            const float xs = best[q] * h2s;
+            const _Float16 h = (_Float16)xs;
+            hi[q] = h;
+            lo[q] = (_Float16)(xs - (float)h);
+        }
+        *reinterpret_cast<h8*>(planes + o) = hi;
+        *reinterpret_cast<h8*>(planes + plane_stride + o) = lo;
+    }
+}
+
+// g = d(z0) (.) [z0 > 0] of the 2 x 2 input block (by, bx), channels 4 cv .. 4 cv + 3, from d(p0) and the argmax bytes: the sums of
+// maxpool_bwd_blk_kernel (the block's four candidate windows in the same order, so the values are bit-equal to the tensor
+// dml_maxpool3x3s2_bwd writes), then the pixel's ReLU mask bits.  Pixels beyond the map stay zero.
+__device__ __forceinline__ void stem_block_grad(const float* __restrict__ dp, const uint8_t* __restrict__ argmax,
+                                                const uint8_t* __restrict__ mask, int b, int by, int bx, int H, int W, int C,
+                                                int Ho, int Wo, int cv, float (&acc)[2][2][4]) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[u][t][q] = 0.f;
+#pragma unroll
+    for (int dyo = 0; dyo < 2; ++dyo) {
+        const int yo = by + dyo;
+        if (yo >= Ho) continue;
+#pragma unroll
+        for (int dxo = 0; dxo < 2; ++dxo) {
+            const int xo = bx + dxo;
+            if (xo >= Wo) continue;
+            const int64_t o = (((int64_t)b * Ho + yo) * Wo + xo) * C + cv * 4;
+            float g[4];
+            Vec16<float>::load(dp + o, g);
+            const uint32_t am = *reinterpret_cast<const uint32_t*>(argmax + o);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int r = 2 * by + u - (2 * yo - 1);           // tap row of input row 2 by + u in this window
+                if (r < 0 || r > 2) continue;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int s = 2 * bx + t - (2 * xo - 1);
+                    if (s < 0 || s > 2) continue;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[u][t][q] += (((am >> (q * 8)) & 0xffu) == (uint32_t)(r * 3 + s)) ? g[q] : 0.f;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int yi = 2 * by + u, xi = 2 * bx + t;
+            if (yi >= H || xi >= W) continue;
+            const uint32_t bits = mask[(((int64_t)b * H + yi) * W + xi) * (C / 4) + cv];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[u][t][q] = ((bits >> q) & 1u) != 0 ? acc[u][t][q] : 0.f;
+        }
+    }
+}
+
+// g of ONE input pixel (row m = (b H + yi) W + xi), channels 4 cv .. 4 cv + 3: its candidate windows in the order in which
+// maxpool_bwd_blk_kernel adds them for this pixel (yo ascending, then xo), then the mask bits
+__device__ __forceinline__ void stem_pixel_grad(const float* __restrict__ dp, const uint8_t* __restrict__ argmax, uint32_t bits, int b,
+                                                int yi, int xi, int C, int Ho, int Wo, int cv, float (&acc)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = 0.f;
+    const int by = yi >> 1, bx = xi >> 1, u = yi & 1, t = xi & 1;
+#pragma unroll
+    for (int dyo = 0; dyo < 2; ++dyo) {
+        const int yo = by + dyo, r = u + 1 - 2 * dyo;           // tap row of this pixel in window yo
+        if (yo >= Ho || r < 0) continue;
+#pragma unroll
+        for (int dxo = 0; dxo < 2; ++dxo) {
+            const int xo = bx + dxo, sc = t + 1 - 2 * dxo;
+            if (xo >= Wo || sc < 0) continue;
+            const int64_t o = (((int64_t)b * Ho + yo) * Wo + xo) * C + cv * 4;
+            float g[4];
+            Vec16<float>::load(dp + o, g);
+            const uint32_t am = *reinterpret_cast<const uint32_t*>(argmax + o);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] += (((am >> (q * 8)) & 0xffu) == (uint32_t)(r * 3 + sc)) ? g[q] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = ((bits >> q) & 1u) != 0 ? acc[q] : 0.f;
+}
+
+// BatchNorm-backward pass 1 of the stem: bn_bwd_reduce_kernel<float> with g gathered per pixel instead of loaded -- the same rows per
+// workgroup and per thread, the same order of additions, so the partial rows are bit-equal to those dml_bn_bwd_reduce writes from
+// the d(z0) tensor of dml_maxpool3x3s2_bwd (and the step's parameter gradients do not move)
+__global__ __launch_bounds__(256) void stem_bwd_reduce_kernel(
+    const float* __restrict__ dp, const uint8_t* __restrict__ argmax, const uint8_t* __restrict__ mask, const float* __restrict__ y,
+    const float* __restrict__ save_mean, const float* __restrict__ save_invstd, float* __restrict__ partials, int B, int H, int W,
+    int C, int ldy, int Ho, int Wo, int rows_per_block, int chv, int rt, uint32_t* __restrict__ gmax) {
+    __shared__ float sh[256 * 2 * 4];
+    uint32_t gmx = 0;
+    const int NV = C / 4;
+    const int64_t M = (int64_t)B * H * W;
+    const int col = threadIdx.x % chv, rl = threadIdx.x / chv;
+    const int v = blockIdx.y * chv + col;
+    const bool active = rl < rt && v < NV;
+    float sg[4], sgx[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { sg[q] = 0.f; sgx[q] = 0.f; }
+    if (active) {
+        const int c = v * 4;
+        float mu[4], is[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { mu[q] = save_mean[c + q]; is[q] = save_invstd[c + q]; }
+        const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+        const int64_t r1 = min(M, r0 + rows_per_block);
+        constexpr int U = 2;                  // rows in flight per thread
+        for (int64_t m0 = r0 + rl; m0 < r1; m0 += (int64_t)rt * U) {
+            float g[U][4], yy[U][4];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t m = m0 + (int64_t)u * rt;
+                if (m < r1) {
+                    const int xi = (int)(m % W), yi = (int)((m / W) % H), b = (int)(m / ((int64_t)W * H));
+                    Vec16<float>::load(y + m * ldy + c, yy[u]);
+                    stem_pixel_grad(dp, argmax, mask[m * NV + v], b, yi, xi, C, Ho, Wo, v, g[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t m = m0 + (int64_t)u * rt;
+                if (m >= r1) continue;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float gg = g[u][q];
+                    gmx = max(gmx, __float_as_uint(gg) & 0x7fffffffu);
+                    sg[q] += gg;
+                    sgx[q] += gg * (yy[u][q] - mu[q]) * is[q];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        sh[(threadIdx.x * 4 + q) * 2] = sg[q];
+        sh[(threadIdx.x * 4 + q) * 2 + 1] = sgx[q];
+    }
+    __syncthreads();
+    if (rl == 0 && v < NV) {
+        for (int r = 1; r < rt; ++r) {
+            const int t = r * chv + col;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                sg[q] += sh[(t * 4 + q) * 2];
+                sgx[q] += sh[(t * 4 + q) * 2 + 1];
+            }
+        }
+        float* pr = partials + ((int64_t)blockIdx.x * C + v * 4) * 2;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { pr[2 * q] = sg[q]; pr[2 * q + 1] = sgx[q]; }
+    }
+    if (gmax != nullptr) amax_publish(gmx, gmax);
+}
+
+// pass 2: dy = coef0 g + coef1 (y - coef3) + coef2 (bn_bwd_apply_cols_kernel's expression), one thread per 2 x 2 block and four channels
+__global__ __launch_bounds__(64) void stem_bwd_apply_kernel(
+    const float* __restrict__ dp, const uint8_t* __restrict__ argmax, const uint8_t* __restrict__ mask, const float* __restrict__ y,
+    const float* __restrict__ coef, float* __restrict__ dy, int B, int H, int W, int C, int ldy, int lddy, int Ho, int Wo,
+    _Float16* __restrict__ planes, int64_t plane_stride, int ldp, const float* __restrict__ unscale) {
+    const float h2s = planes != nullptr ? 1.0f / unscale[0] : 1.0f;
+    const int NV = C / 4, Hb = (H + 1) / 2, Wb = (W + 1) / 2;
+    const int64_t total = (int64_t)B * Hb * Wb * NV;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int v = (int)(i % NV);
+    int64_t pix = i / NV;
+    const int bx = (int)(pix % Wb); pix /= Wb;
+    const int by = (int)(pix % Hb);
+    const int b = (int)(pix / Hb);
+    const int c = v * 4;
+    float yy[2][2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int yi = 2 * by + u, xi = 2 * bx + t;
+            if (yi < H && xi < W) Vec16<float>::load(y + (((int64_t)b * H + yi) * W + xi) * ldy + c, yy[u][t]);
+        }
+    float cA[4], cB[4], cC[4], cM[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        cA[q] = coef[c + q];
+        cB[q] = coef[C + c + q];
+        cC[q] = coef[2 * C + c + q];
+        cM[q] = coef[3 * C + c + q];
+    }
+    float g[2][2][4];
+    stem_block_grad(dp, argmax, mask, b, by, bx, H, W, C, Ho, Wo, v, g);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int yi = 2 * by + u, xi = 2 * bx + t;
+            if (yi >= H || xi >= W) continue;
+            const int64_t m = ((int64_t)b * H + yi) * W + xi;
+            float o[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = cA[q] * g[u][t][q] + cB[q] * (yy[u][t][q] - cM[q]) + cC[q];
+            if (dy != nullptr) Vec16<float>::store(dy + m * lddy + c, o);
+            if (planes != nullptr) h2_store4(planes + m * ldp + c, planes + plane_stride + m * ldp + c, o, h2s);
+        }
+}
+}  // namespace
+
+extern "C" int dml_bn_relu_maxpool3x3s2_fwd(const void* y, const float* scale, const float* shift, const float* mean, void* p,
+                                            uint8_t* argmax, uint8_t* mask, void* planes, int64_t plane_stride,
+                                            const float* unscale, float* amax, int B, int H, int W, int C, int ldy, void* stream) {
+    if (!y || !scale || !shift || !mean || (!p && !planes) || B <= 0 || H <= 0 || W <= 0 || C <= 0) return DML_EINVAL;
+    if ((C & 7) || (ldy & 3) || ldy < C || (reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(p) & 15) ||
+        (reinterpret_cast<uintptr_t>(argmax) & 7) || (reinterpret_cast<uintptr_t>(mask) & 1))
+        return DML_EALIGN;
+    if (planes) {
+        if (!unscale || plane_stride <= 0) return DML_EINVAL;
+        if ((plane_stride & 7) || (reinterpret_cast<uintptr_t>(planes) & 15)) return DML_EALIGN;
+    }
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int64_t items = (int64_t)B * Ho * Wo * (C / 8);
+    if ((int64_t)B * H * W >= (1ll << 31) || items >= (1ll << 31) * 256) return DML_EINVAL;
+    // one item per thread: short-lived workgroups sweep the tensor front to back (dml_maxpool3x3s2_fwd)
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (const float*)y, scale, shift, mean, (float*)p, argmax, mask, static_cast<_Float16*>(planes), plane_stride,
+                       unscale, reinterpret_cast<uint32_t*>(amax), B, H, W, C, ldy, Ho, Wo);
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+static bool stem_bwd_args_ok(const void* dp, const uint8_t* argmax, const uint8_t* mask, const void* y, int B, int H, int W, int C,
+                             int ldy, int& rc) {
+    rc = 0;
+    if (!dp || !argmax || !mask || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0) rc = DML_EINVAL;
+    else if ((C & 3) || (ldy & 3) || ldy < C || (reinterpret_cast<uintptr_t>(dp) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
+             (reinterpret_cast<uintptr_t>(argmax) & 3))
+        rc = DML_EALIGN;
+    else if ((int64_t)B * H * W >= (1ll << 31)) rc = DML_EINVAL;
+    return rc == 0;
+}
+
+extern "C" int dml_stem_bn_bwd_reduce(const void* dp, const uint8_t* argmax, const uint8_t* mask, const void* y,
+                                      const float* save_mean, const float* save_invstd, float* partials, int B, int H, int W,
+                                      int C, int ldy, int* nblocks, float* gmax, void* stream) {
+    int rc;
+    if (!stem_bwd_args_ok(dp, argmax, mask, y, B, H, W, C, ldy, rc)) return rc;
+    if (!save_mean || !save_invstd || !partials || !nblocks) return DML_EINVAL;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int NV = C / 4;
+    const int chv = NV < RED_COLS ? NV : RED_COLS;
+    const int rt = 256 / chv;
+    const int col_chunks = (NV + chv - 1) / chv;
+    const int64_t M = (int64_t)B * H * W;       // (the geometry of dml_bn_bwd_reduce: the same partial rows)
+    int64_t rpb = (M * col_chunks + 1023) / 1024;
+    if (rpb < 4 * rt) rpb = 4 * rt;
+    rpb = ((rpb + rt - 1) / rt) * rt;
+    const int rb = (int)((M + rpb - 1) / rpb);
+    *nblocks = rb;
+    hipLaunchKernelGGL(stem_bwd_reduce_kernel, dim3(rb, col_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), (const float*)dp,
+                       argmax, mask, (const float*)y, save_mean, save_invstd, partials, B, H, W, C, ldy, Ho, Wo, (int)rpb, chv, rt,
+                       reinterpret_cast<uint32_t*>(gmax));
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dml_stem_bn_bwd_apply(const void* dp, const uint8_t* argmax, const uint8_t* mask, const void* y, const float* coef,
+                                     void* dy, int B, int H, int W, int C, int ldy, int lddy, void* planes, int64_t plane_stride,
+                                     int32_t ldp, const float* unscale, void* stream) {
+    int rc;
+    if (!stem_bwd_args_ok(dp, argmax, mask, y, B, H, W, C, ldy, rc)) return rc;
+    if (!coef || (!dy && !planes)) return DML_EINVAL;
+    if (dy && ((lddy & 3) || lddy < C || (reinterpret_cast<uintptr_t>(dy) & 15))) return DML_EALIGN;
+    if (planes) {
+        if (!unscale || plane_stride <= 0 || ldp < C) return DML_EINVAL;
+        if ((ldp & 3) || (plane_stride & 3) || (reinterpret_cast<uintptr_t>(planes) & 7)) return DML_EALIGN;
+    }
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int64_t items = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
+    if (items >= (1ll << 31) * 64) return DML_EINVAL;
+    // one-wave workgroups, as dml_bn_bwd_apply: they start beside the side stream's weight-gradient workgroups
+    hipLaunchKernelGGL(stem_bwd_apply_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       (const float*)dp, argmax, mask, (const float*)y, coef, (float*)dy, B, H, W, C, ldy, lddy, Ho, Wo,
+                       static_cast<_Float16*>(planes), plane_stride, (int)ldp, unscale);
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the decoder unit in front of the embedding conv: its output gradient formed on the fly -------------------------------------
+// d(z) of that unit is the data gradient of a 1x1 convolution with K <= 32 output channels: dz[m][c] = sum_k de[m][k] W[k][c], a
+// rank-K product.  As a tensor it is 604 MB (16 x 192 x 192 x 256) that the two BatchNorm-backward passes read once each; `de` is 38
+// MB.  These variants of bn_bwd_reduce_kernel / bn_bwd_apply_cols_kernel (fp32, ReLU from the bit mask) keep their four channels'
+// columns of W in registers and form dz per row with KP fp32 FMAs in the order k = 0 .. KP - 1.
+namespace {
+template <int KP>
+__device__ __forceinline__ void head_load_w(const float* __restrict__ w, int K, int ldw, int c, float (&wr)[KP][4]) {
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wr[k][q] = k < K ? w[(int64_t)k * ldw + c + q] : 0.f;
+    }
+}
+template <int KP>
+__device__ __forceinline__ void head_load_de(const float* __restrict__ de_row, float (&d)[KP]) {
+#pragma unroll
+    for (int k = 0; k < KP; k += 4) {
+        const float4 t = *reinterpret_cast<const float4*>(de_row + k);
+        d[k] = t.x; d[k + 1] = t.y; d[k + 2] = t.z; d[k + 3] = t.w;
+    }
+}
+template <int KP>
+__device__ __forceinline__ void head_dz(const float (&d)[KP], const float (&wr)[KP][4], float (&g)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) a = fmaf(d[k], wr[k][q], a);
+        g[q] = a;
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void head_bwd_reduce_kernel(
+    const float* __restrict__ de, const float* __restrict__ w, const float* __restrict__ y, const uint8_t* __restrict__ mask,
+    const float* __restrict__ save_mean, const float* __restrict__ save_invstd, float* __restrict__ partials, int64_t M, int N,
+    int K, int ldde, int ldw, int ldy, int relu, int rows_per_block, int chv, int rt, uint32_t* __restrict__ gmax) {
+    __shared__ float sh[256 * 2 * 4];
+    uint32_t gmx = 0;
+    const int NV = N / 4;
+    const int col = threadIdx.x % chv, rl = threadIdx.x / chv;
+    const int v = blockIdx.y * chv + col;
+    const bool active = rl < rt && v < NV;
+    float sg[4], sgx[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { sg[q] = 0.f; sgx[q] = 0.f; }
+    if (active) {
+        const int c = v * 4;
+        float mu[4], is[4], wr[KP][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { mu[q] = save_mean[c + q]; is[q] = save_invstd[c + q]; }
+        head_load_w<KP>(w, K, ldw, c, wr);
+        const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+        const int64_t r1 = min(M, r0 + rows_per_block);
+        constexpr int U = 2;                  // rows in flight per thread
+        for (int64_t m0 = r0 + rl; m0 < r1; m0 += (int64_t)rt * U) {
+            float d[U][KP], yy[U][4];
+            uint32_t bits[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t m = m0 + (int64_t)u * rt;
+                bits[u] = 0xfu;
+                if (m < r1) {
+                    head_load_de<KP>(de + m * ldde, d[u]);
+                    Vec16<float>::load(y + m * ldy + c, yy[u]);
+                    if (relu) bits[u] = mask[m * NV + v];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t m = m0 + (int64_t)u * rt;
+                if (m >= r1) continue;
+                float g[4];
+                head_dz<KP>(d[u], wr, g);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float gg = ((bits[u] >> q) & 1u) != 0 ? g[q] : 0.f;
+                    gmx = max(gmx, __float_as_uint(gg) & 0x7fffffffu);
+                    sg[q] += gg;
+                    sgx[q] += gg * (yy[u][q] - mu[q]) * is[q];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        sh[(threadIdx.x * 4 + q) * 2] = sg[q];
+        sh[(threadIdx.x * 4 + q) * 2 + 1] = sgx[q];
+    }
+    __syncthreads();
+    if (rl == 0 && v < NV) {
+        for (int r = 1; r < rt; ++r) {
+            const int t = r * chv + col;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                sg[q] += sh[(t * 4 + q) * 2];
+                sgx[q] += sh[(t * 4 + q) * 2 + 1];
+            }
+        }
+        float* p = partials + ((int64_t)blockIdx.x * N + v * 4) * 2;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { p[2 * q] = sg[q]; p[2 * q + 1] = sgx[q]; }
+    }
+    if (gmax != nullptr) amax_publish(gmx, gmax);
+}
+
+// PAIR: dy leaves as planes only and N % 8 == 0 -- the lanes 2 j, 2 j + 1 of a row hold channels 8 j .. 8 j + 7 between them; they swap
+// halves so that the even lane stores the eight hi values and the odd lane the eight lo values as ONE 16-byte vector each (the
+// planes in 8-byte pieces run at 0.54-0.70 x the rate per instruction, bn_apply_planes8_kernel)
+template <int KP, int U, bool PAIR>
+__global__ __launch_bounds__(64) void head_bwd_apply_kernel(
+    const float* __restrict__ de, const float* __restrict__ w, const float* __restrict__ y, const uint8_t* __restrict__ mask,
+    const float* __restrict__ coef, float* __restrict__ dy, int64_t M, int N, int K, int ldde, int ldw, int ldy, int lddy, int relu,
+    int CB, int RB, int rows_per_block, _Float16* __restrict__ planes, int64_t plane_stride, int ldp,
+    const float* __restrict__ unscale) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const float h2s = planes != nullptr ? 1.0f / unscale[0] : 1.0f;
+    const int NV = N / 4;
+    const int col = threadIdx.x % CB, rl = threadIdx.x / CB;
+    const int vcol = blockIdx.y * CB + col;
+    if (!(rl < RB && vcol < NV)) return;      // (PAIR: CB and NV are even, so both lanes of a pair stay or leave)
+    const int c = vcol * 4;
+    float cA[4], cB[4], cC[4], cM[4], wr[KP][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        cA[q] = coef[c + q];
+        cB[q] = coef[N + c + q];
+        cC[q] = coef[2 * N + c + q];
+        cM[q] = coef[3 * N + c + q];
+    }
+    head_load_w<KP>(w, K, ldw, c, wr);
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r1 = min(M, r0 + rows_per_block);
+    for (int64_t m0 = r0 + rl; m0 < r1; m0 += (int64_t)RB * U) {
+        float d[U][KP], yy[U][4];
+        uint32_t bits[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t m = m0 + (int64_t)u * RB;
+            bits[u] = 0xfu;
+            if (m < r1) {
+                head_load_de<KP>(de + m * ldde, d[u]);
+                Vec16<float>::load(y + m * ldy + c, yy[u]);
+                if (relu) bits[u] = mask[m * NV + vcol];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t m = m0 + (int64_t)u * RB;
+            if (m >= r1) continue;
+            float g[4], o[4];
+            head_dz<KP>(d[u], wr, g);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                g[q] = ((bits[u] >> q) & 1u) != 0 ? g[q] : 0.f;
+                o[q] = cA[q] * g[q] + cB[q] * (yy[u][q] - cM[q]) + cC[q];
+            }
+            if (dy != nullptr) Vec16<float>::store(dy + m * lddy + c, o);
+            if constexpr (PAIR) {
+                h4 hi, lo;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float xs = o[q] * h2s;
+                    const _Float16 h = (_Float16)xs;
+                    hi[q] = h;
+                    lo[q] = (_Float16)(xs - (float)h);
+                }
+                const uint2 hb = __builtin_bit_cast(uint2, hi), lb = __builtin_bit_cast(uint2, lo);
+                const bool odd = (threadIdx.x & 1) != 0;
+                const uint2 send = odd ? hb : lb;          // what the other lane of the pair stores
+                const uint32_t rx = (uint32_t)__shfl_xor((int)send.x, 1, 64), ry = (uint32_t)__shfl_xor((int)send.y, 1, 64);
+                if (!odd) *reinterpret_cast<uint4*>(planes + m * ldp + c) = make_uint4(hb.x, hb.y, rx, ry);
+                else *reinterpret_cast<uint4*>(planes + plane_stride + m * ldp + c - 4) = make_uint4(rx, ry, lb.x, lb.y);
+            } else {
+                if (planes != nullptr) h2_store4(planes + m * ldp + c, planes + plane_stride + m * ldp + c, o, h2s);
+            }
+        }
+    }
+}
+
+static int head_bwd_args(const void* de, const float* w, const void* y, const uint8_t* mask, int64_t M, int N, int K, int Kp,
+                         int ldde, int ldw, int ldy, int relu) {
+    if (!de || !w || !y || (relu && !mask) || M <= 0 || N <= 0 || K <= 0 || K > Kp) return DML_EINVAL;
+    if (Kp != 8 && Kp != 16 && Kp != 24 && Kp != 32) return DML_EINVAL;
+    if ((N & 3) || (ldy & 3) || ldy < N || (ldde & 3) || ldde < Kp || ldw < N || (reinterpret_cast<uintptr_t>(de) & 15) ||
+        (reinterpret_cast<uintptr_t>(y) & 15))
+        return DML_EALIGN;
+    if (M >= (1ll << 31)) return DML_EINVAL;
+    return 0;
+}
+}  // namespace
+
+extern "C" int dml_head_bn_bwd_reduce(const void* de, const float* w, const void* y, const uint8_t* mask, const float* save_mean,
+                                      const float* save_invstd, float* partials, int64_t M, int N, int K, int Kp, int ldde, int ldw,
+                                      int ldy, int relu, int* nblocks, float* gmax, void* stream) {
+    if (const int rc = head_bwd_args(de, w, y, mask, M, N, K, Kp, ldde, ldw, ldy, relu)) return rc;
+    if (!save_mean || !save_invstd || !partials || !nblocks) return DML_EINVAL;
+    const int NV = N / 4;                  // (the geometry of dml_bn_bwd_reduce)
+    const int chv = NV < RED_COLS ? NV : RED_COLS;
+    const int rt = 256 / chv;
+    const int col_chunks = (NV + chv - 1) / chv;
+    int64_t rpb = (M * col_chunks + 1023) / 1024;
+    if (rpb < 4 * rt) rpb = 4 * rt;
+    rpb = ((rpb + rt - 1) / rt) * rt;
+    const int rb = (int)((M + rpb - 1) / rpb);
+    *nblocks = rb;
+    const dim3 grid(rb, col_chunks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define DML_HEAD_REDUCE(KP)                                                                                                       \
+    hipLaunchKernelGGL(head_bwd_reduce_kernel<KP>, grid, dim3(256), 0, st, (const float*)de, w, (const float*)y, mask, save_mean, \
+                       save_invstd, partials, M, N, K, ldde, ldw, ldy, relu, (int)rpb, chv, rt, reinterpret_cast<uint32_t*>(gmax))
+    if (Kp == 8) DML_HEAD_REDUCE(8);
+    else if (Kp == 16) DML_HEAD_REDUCE(16);
+    else if (Kp == 24) DML_HEAD_REDUCE(24);
+    else DML_HEAD_REDUCE(32);
+#undef DML_HEAD_REDUCE
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dml_head_bn_bwd_apply(const void* de, const float* w, const void* y, const uint8_t* mask, const float* coef, void* dy,
+                                     int64_t M, int N, int K, int Kp, int ldde, int ldw, int ldy, int lddy, int relu, void* planes,
+                                     int64_t plane_stride, int32_t ldp, const float* unscale, void* stream) {
+    if (const int rc = head_bwd_args(de, w, y, mask, M, N, K, Kp, ldde, ldw, ldy, relu)) return rc;
+    if (!coef || (!dy && !planes)) return DML_EINVAL;
+    if (dy && ((lddy & 3) || lddy < N || (reinterpret_cast<uintptr_t>(dy) & 15))) return DML_EALIGN;
+    if (planes) {
+        if (!unscale || plane_stride <= 0 || ldp < N) return DML_EINVAL;
+        if ((ldp & 3) || (plane_stride & 3) || (reinterpret_cast<uintptr_t>(planes) & 7)) return DML_EALIGN;
+    }
+    constexpr int bt = 64;                 // one-wave workgroups, as dml_bn_bwd_apply
+    const ColGeom g = col_geom(M, N / 4, 2, stream_blocks(M, N, DML_F32), bt);
+    const dim3 grid(g.row_blocks, g.col_chunks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool pair = planes && !dy && (N & 7) == 0 && (ldp & 7) == 0 && (plane_stride & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(planes) & 15) == 0;
+#define DML_HEAD_APPLY(KP, PAIR)                                                                                                   \
+    hipLaunchKernelGGL((head_bwd_apply_kernel<KP, 2, PAIR>), grid, dim3(bt), 0, st, (const float*)de, w, (const float*)y, mask, coef, \
+                       (float*)dy, M, N, K, ldde, ldw, ldy, lddy, relu, g.CB, g.RB, g.rows_per_block,                              \
+                       static_cast<_Float16*>(planes), plane_stride, (int)ldp, unscale)
+    if (pair) {
+        if (Kp == 8) DML_HEAD_APPLY(8, true);
+        else if (Kp == 16) DML_HEAD_APPLY(16, true);
+        else if (Kp == 24) DML_HEAD_APPLY(24, true);
+        else DML_HEAD_APPLY(32, true);
+    } else {
+        if (Kp == 8) DML_HEAD_APPLY(8, false);
+        else if (Kp == 16) DML_HEAD_APPLY(16, false);
+        else if (Kp == 24) DML_HEAD_APPLY(24, false);
+        else DML_HEAD_APPLY(32, false);
+    }
+#undef DML_HEAD_APPLY
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- scale of a BatchNorm output's fp16 planes from a BOUND on its magnitude, known before the tensor exists -----------
 // Batch statistics bound the normalised value: sum_m (y_m - mean)^2 = count * var, so |y_m - mean| * invstd <= sqrt(count)
 // for every element, whatever the data.  Forward:  |z| <= max_c (|gamma_c| sqrt(count) + |beta_c|) * mult + max |res|.

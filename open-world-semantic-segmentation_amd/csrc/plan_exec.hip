@@ -122,6 +122,11 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_bilinear_fwd_planes),
     DML_ENTRY(dml_bn_finalize_bound),
     DML_ENTRY(dml_bn_bwd_finalize_bound),
+    DML_ENTRY(dml_bn_relu_maxpool3x3s2_fwd),
+    DML_ENTRY(dml_stem_bn_bwd_reduce),
+    DML_ENTRY(dml_stem_bn_bwd_apply),
+    DML_ENTRY(dml_head_bn_bwd_reduce),
+    DML_ENTRY(dml_head_bn_bwd_apply),
 };
 constexpr int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));
 

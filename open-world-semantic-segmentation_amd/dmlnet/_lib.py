@@ -155,6 +155,13 @@ _PROTOS = {
     "dml_bn_bwd_finalize": (c_i, [c_p, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "dml_bn_bwd_apply": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f,
                                c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
+    "dml_bn_relu_maxpool3x3s2_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "dml_stem_bn_bwd_reduce": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_p, c_p]),
+    "dml_stem_bn_bwd_apply": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_i, c_p, c_p]),
+    "dml_head_bn_bwd_reduce": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                     C.POINTER(c_i), c_p, c_p]),
+    "dml_head_bn_bwd_apply": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64,
+                                    c_i, c_p, c_p]),
     "dml_h2_bound_bn": (c_i, [c_p, c_p, c_i, c_i64, c_f, c_p, c_p, c_p]),
     "dml_h2_bound_bn_table": (c_i, [c_p, c_i, c_p]),
     "dml_h2_bound_bn_multi": (c_i, [c_p, c_i, c_p, c_p]),

@@ -384,6 +384,12 @@ class Plan:
         # f16x2: data gradients of the stride-2 convolutions as stride-1 launches per pixel-parity class (conv_dgrad_s2_classes).
         # DML_S2_CLASSES=0: off (A/B, tests)
         self.s2_classes_on = os.environ.get("DML_S2_CLASSES", "1") != "0"
+        # f16x2 training: the stem's BatchNorm + ReLU + max pool as one pass each way (dml_bn_relu_maxpool3x3s2_fwd / dml_stem_bn_bwd_*):
+        # z0 and d(z0), 604 MB each at 16 x 384 x 384 x 64, are never written.  DML_FUSE_STEM=0: off (A/B, tests)
+        self.fuse_stem_on = os.environ.get("DML_FUSE_STEM", "1") != "0"
+        # f16x2 training: the decoder unit's BatchNorm backward forms the embedding conv's data gradient itself (dml_head_bn_bwd_*)
+        # instead of reading it back twice from a 604 MB tensor.  DML_FUSE_HEAD_DGRAD=0: off (A/B, tests)
+        self.fuse_head_dgrad_on = os.environ.get("DML_FUSE_HEAD_DGRAD", "1") != "0"
         self.prep_overlap_on = os.environ.get("DML_PREP_OVERLAP", "1") != "0"      # refresh_weights (A/B)
         self.ds_grad_from_dz = os.environ.get("DML_DS_GRAD_FROM_DZ", "1") != "0"      # block_bwd (A/B)
         self.prep_gather = []          # dml_gather_taps argument lists: sub-filters of the transposed weight copies, refreshed with them
@@ -821,9 +827,12 @@ class Plan:
         self.param_last_op[self.e.store._index(p)] = len(self.bwd) - 1
 
     def cbr(self, x: Act, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu=True, res: Optional[Act] = None,
-            out: Optional[Act] = None, drop: Optional[nn.Dropout] = None, need_dgrad=True, planes_only=False) -> ConvUnit:
+            out: Optional[Act] = None, drop: Optional[nn.Dropout] = None, need_dgrad=True, planes_only=False,
+            pool_fused=False) -> ConvUnit:
         """conv -> BN(batch or running stats) -> (+res) -> (ReLU) -> (dropout); z may be a concat slice.
-        planes_only: only planes consumers read z (the convolutions of an f16x2 plan) -- no fp32 z where the BN writes planes."""
+        planes_only: only planes consumers read z (the convolutions of an f16x2 plan) -- no fp32 z where the BN writes planes.
+        pool_fused: the caller applies the BatchNorm inside its pooling pass (the stem, Plan.build): conv and statistics only, the unit
+        has no z (its mask is the caller's to fill)."""
         lib, st = self.lib, self.e.store
         u = ConvUnit()
         u.conv, u.bn, u.x, u.relu, u.res, u.drop = conv, bn, x, relu, res, drop
@@ -836,9 +845,12 @@ class Plan:
         # f16x2 training: this BN writes z's fp16 planes itself (Plan.h2_direct) -- batch statistics bound the output
         direct = (self.h2_direct_on and self.training and bn.training and self.f32_split == 2 and self.dtype == torch.float32
                   and out is None and N % 8 == 0 and drop is None
-                  and (res is None or (res is res.root and res.amax is not None)))
+                  and (res is None or (res is res.root and res.amax is not None)) and not pool_fused)
         planes_only = planes_only and direct and self.planes_fit(x.B * Ho * Wo, N)
-        if direct:
+        if pool_fused:
+            assert self.training and bn.training and relu and res is None and out is None and drop is None and not self.sync
+            u.z = None
+        elif direct:
             u.z = self.h2_direct(x.B, Ho, Wo, N, fp32_too=not planes_only)
             if not planes_only or res is not None:
                 # max |z| is published where something may ask for it: a conv reading the fp32 tensor through dml_h2_split, or the
@@ -847,7 +859,7 @@ class Plan:
         else:
             u.z = out if out is not None else self.new(x.B, Ho, Wo, N)
         u.y = self.new(x.B, Ho, Wo, N) if self.training else None      # inference never materialises it
-        M = u.z.M
+        M = x.B * Ho * Wo
         u.scale, u.shift = self.fbuf(N), self.fbuf(N)
         g_ptr, b_ptr = bn.weight.data_ptr(), bn.bias.data_ptr()
         mean_ptr = bn.running_mean.data_ptr()
@@ -915,6 +927,10 @@ class Plan:
             u.mask = torch.empty(M * (N // self.vec), dtype=torch.uint8, device=self.device)
             self.keep.append(u.mask)
         mask_ptr = u.mask.data_ptr() if u.mask is not None else None
+        if pool_fused:
+            u.apply_args = None
+            self.units.append(u)
+            return u
         pl = (None, 0, 0, None)
         if direct:
             planes, work = u.z.h2
@@ -952,14 +968,16 @@ class Plan:
         self.units.append(u)
         return u
 
-    def unit_bwd(self, u: ConvUnit, dz: Act, dres: Optional[Act] = None, dres_accum=False, need_dgrad=True, final=True,
-                 up_mask=None):
+    def unit_bwd(self, u: ConvUnit, dz: Optional[Act], dres: Optional[Act] = None, dres_accum=False, need_dgrad=True, final=True,
+                 up_mask=None, dz_from=None):
         """Backward of `cbr`: BN (two passes) -> weight gradient -> data gradient into u.x.grad (`final`: conv_dgrad).
         up_mask: `dz` is the gradient of a LATER ReLU's output and `up_mask` that ReLU's 1-bit mask -- this unit's own output gradient
-        is dz (.) mask, formed on the fly by the two BN passes (block_bwd: the downsample branch reads the block output's gradient)."""
+        is dz (.) mask, formed on the fly by the two BN passes (block_bwd: the downsample branch reads the block output's gradient).
+        dz_from = (de, w, K), with dz None: the output gradient is the data gradient of a 1x1 convolution with K output channels
+        behind this unit, de [M][Kp] times its weight w [K][N], and the two BN passes form it themselves (_head_bwd, dml_head_bn_bwd_*)."""
         if u.dtype != self.dtype:
             with self.precision(u.dtype):
-                return self.unit_bwd(u, dz, dres, dres_accum, need_dgrad, final, up_mask)
+                return self.unit_bwd(u, dz, dres, dres_accum, need_dgrad, final, up_mask, dz_from)
         lib, st = self.lib, self.e.store
         N, M = u.conv.out_channels, u.y.M
         bn = u.bn
@@ -991,13 +1009,16 @@ class Plan:
         # no dropout scale, at most 4096 row groups (on the 192 x 192 layers the finalize would fold 9216 groups in two
         # stages, which works, but the fused sums then cost the data gradients more than the stand-alone reduce:
         # 363.5 vs 364.5 images/s).
-        prod = self.last_dgrad.get(dz.ptr) if (self.fuse_bn_reduce and u.z is u.z.root and up_mask is None) else None
+        if dz_from is not None:
+            assert dz is None and dres is None and up_mask is None and u.drop is None and (u.mask is not None or not u.relu)
+        prod = self.last_dgrad.get(dz.ptr) if (self.fuse_bn_reduce and dz is not None and u.z is u.z.root and up_mask is None) else None
         # (a stride-2 data gradient issued as four parity-class launches: each writes the sums of its own rows, conv_dgrad_s2_classes)
         prods = prod if isinstance(prod, list) else ([prod] if prod is not None else [])
         prod = prods[0] if prods else None
         prows = lib.dml_conv_stat_rows(C.byref(prod)) if prod is not None else STAT_ROWS      # rows per partial of that launch
         Gs = [(pd.B * pd.Ho * pd.Wo + prows - 1) // prows for pd in prods] if len(prods) > 1 else [(M + prows - 1) // prows]
         G = sum(Gs)
+        de, de_w, de_k = dz_from if dz_from is not None else (None, None, 0)
         fused = (prod is not None and len(prods) == 1 and self.dtype == torch.bfloat16 and (u.mask is not None or not u.relu)
                  and u.drop is None and N % 8 == 0 and N > 32 and G <= 4096 and prod.N == N and prod.ldy == N
                  and dz.ld == N and prod.y == dz.ptr)
@@ -1023,6 +1044,11 @@ class Plan:
             nblk = C.c_int(G)
             self.keep.append(nblk)
             sp = part.data_ptr()
+        elif de is not None:
+            sp = self.sp
+            self.call(self.bwd, lib.dml_head_bn_bwd_reduce, de.ptr, de_w, u.y.ptr, mk, u.mean.data_ptr(), u.invstd.data_ptr(),
+                      self.sp, M, N, de_k, de.C, de.ld, N, u.y.ld, 1 if relu_eff else 0, C.byref(nblk),
+                      gwork.data_ptr() if gwork is not None else None)
         else:
             sp = self.sp
             a1 = self.call(self.bwd, lib.dml_bn_bwd_reduce, dz.ptr, u.y.ptr, u.z.ptr, mk, u.mean.data_ptr(),
@@ -1056,16 +1082,63 @@ class Plan:
                 self.call(self.bwd, lib.dml_h2_bound_bn_bwd, coef.data_ptr(), u.invstd.data_ptr(), N, M * self.world,
                           gwork.data_ptr(), work.data_ptr())
             pl = (planes.data_ptr(), M * N, N, work.data_ptr() + 4096)
-        a3 = self.call(self.bwd, lib.dml_bn_bwd_apply, dz.ptr, u.y.ptr, u.z.ptr, mk, coef.data_ptr(),
-                       None if only else dy.ptr, dres.ptr if dres is not None else None, M, N, dz.ld, u.y.ld, u.z.ld, dy.ld,
-                       dres.ld if dres is not None else 0, 1 if relu_eff else 0, 1.0,
-                       1 if dres_accum else 0, self.dt, None if dy_direct else self.amax_of(dy), *pl)
-        u.gscale_slots += ([(a1, 13)] if a1 is not None else []) + [(a3, 15)]
+        if de is not None:
+            assert dy_direct
+            self.call(self.bwd, lib.dml_head_bn_bwd_apply, de.ptr, de_w, u.y.ptr, mk, coef.data_ptr(), None if only else dy.ptr,
+                      M, N, de_k, de.C, de.ld, N, u.y.ld, dy.ld, 1 if relu_eff else 0, *pl)
+        else:
+            a3 = self.call(self.bwd, lib.dml_bn_bwd_apply, dz.ptr, u.y.ptr, u.z.ptr, mk, coef.data_ptr(),
+                           None if only else dy.ptr, dres.ptr if dres is not None else None, M, N, dz.ld, u.y.ld, u.z.ld, dy.ld,
+                           dres.ld if dres is not None else 0, 1 if relu_eff else 0, 1.0,
+                           1 if dres_accum else 0, self.dt, None if dy_direct else self.amax_of(dy), *pl)
+            u.gscale_slots += ([(a1, 13)] if a1 is not None else []) + [(a3, 15)]
         if dres is not None:
             self.last_dgrad.pop(dres.ptr, None)   # written by the BN kernel, not by a data gradient
         self.conv_wgrad(u.x, dy, u.conv, u.Cp)
         if need_dgrad:
             self.conv_dgrad(dy, u.conv, u.wt, u.x, final=final)
+
+    def stem_bwd_fused(self, u: ConvUnit, dp: Act, argmax):
+        """Backward of the fused stem (Plan.build, fuse_stem): max pool + BatchNorm backward without d(z0).  Both BatchNorm passes gather
+        a pixel's gradient from d(p0) and the argmax bytes and gate it with the stem's ReLU mask -- what dml_maxpool3x3s2_bwd followed by
+        unit_bwd computes, bit for bit, partial sums included -- then the weight gradient as in unit_bwd.  dy exists in
+        fp32 and / or as planes, whichever the weight gradient reads (conv_wgrad)."""
+        lib, st = self.lib, self.e.store
+        N, M, bn, y = u.conv.out_channels, u.y.M, u.bn, u.y
+        planes = u.x.C % 8 == 0 and N % 8 == 0                # conv_wgrad's test: both operands as planes
+        gwork = None
+        if planes:
+            only = self.planes_fit(M, N) and self.planes_fit(u.x.root.M, u.x.root.ld)
+            dy = self.h2_direct(y.B, y.H, y.W, N, fp32_too=not only)
+            gwork = self.h2_work()
+        else:
+            only = False
+            dy = self.new(y.B, y.H, y.W, N)
+        u.dz, u.dy, u.up = None, dy, None
+        coef = self.fbuf(4 * N)
+        nblk = C.c_int(0)
+        self.keep.append(nblk)
+        self.call(self.bwd, lib.dml_stem_bn_bwd_reduce, dp.ptr, argmax.data_ptr(), u.mask.data_ptr(), y.ptr, u.mean.data_ptr(),
+                  u.invstd.data_ptr(), self.sp, y.B, y.H, y.W, N, y.ld, C.byref(nblk),
+                  gwork.data_ptr() if gwork is not None else None)
+        pl = (None, 0, 0, None)
+        if planes and self.fuse_bound:
+            self.call(self.bwd, lib.dml_bn_bwd_finalize_bound, self.sp, nblk, M, N, bn.weight.data_ptr(), u.mean.data_ptr(),
+                      u.invstd.data_ptr(), st.grad_ptr_of(bn.weight), st.grad_ptr_of(bn.bias), coef.data_ptr(), M,
+                      gwork.data_ptr(), dy.h2[1].data_ptr(), self.bound_state())
+        else:
+            self.call(self.bwd, lib.dml_bn_bwd_finalize, self.sp, nblk, M, N, bn.weight.data_ptr(), u.mean.data_ptr(),
+                      u.invstd.data_ptr(), st.grad_ptr_of(bn.weight), st.grad_ptr_of(bn.bias), coef.data_ptr())
+            if planes:
+                self.call(self.bwd, lib.dml_h2_bound_bn_bwd, coef.data_ptr(), u.invstd.data_ptr(), N, M, gwork.data_ptr(),
+                          dy.h2[1].data_ptr())
+        self.mark_grad(bn.weight)
+        self.mark_grad(bn.bias)
+        if planes:
+            pl = (dy.h2[0].data_ptr(), M * N, N, dy.h2[1].data_ptr() + 4096)
+        self.call(self.bwd, lib.dml_stem_bn_bwd_apply, dp.ptr, argmax.data_ptr(), u.mask.data_ptr(), y.ptr, coef.data_ptr(),
+                  None if only else dy.ptr, y.B, y.H, y.W, N, y.ld, dy.ld, *pl)
+        self.conv_wgrad(u.x, dy, u.conv, u.Cp)
 
     def block_fwd(self, x: Act, blk: nn.Module, out_planes_only=False):
         """one Bottleneck (resnet.py:95-115): 1x1 -> 3x3 -> 1x1, + identity or downsample branch, ReLU.
@@ -1171,14 +1244,26 @@ class Plan:
             self.images_args = self.call(self.fwd, lib.dml_pack_input, 0, x_in.ptr, B, 3, H, W, _PAD_CIN, self.dt)
 
         # stem: 7x7 s2 conv + BN + ReLU, 3x3 s2 max pool (resnet.py:139-143,196-199)
-        stem = self.cbr(x_in, stem_conv, bb.bn1, need_dgrad=False)
-        z0 = stem.z
-        Hp, Wp = (z0.H - 1) // 2 + 1, (z0.W - 1) // 2 + 1
-        p0 = self.new(B, Hp, Wp, 64)
+        Hs, Ws = self.conv_geom(stem_conv, x_in)[5:]
+        Hp, Wp = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
+        # f16x2 training: BatchNorm + ReLU + max pool in ONE pass over y (dml_bn_relu_maxpool3x3s2_fwd).  z0 is never written; the kernel
+        # also collects max |p0|, so the split of p0 needs no maximum pass and scales its planes exactly as before (the step's results
+        # do not move by a bit); the stem's ReLU mask is still written (38 MB: the backward's gate, Plan.stem_bwd_fused)
+        fuse_stem = (self.fuse_stem_on and self.training and self.f32_split == 2 and self.dtype == torch.float32 and not self.sync
+                     and bb.bn1.training and stem_conv.out_channels == 64)
+        stem = self.cbr(x_in, stem_conv, bb.bn1, need_dgrad=False, pool_fused=fuse_stem)
         amax = torch.empty(B * Hp * Wp * 64, dtype=torch.uint8, device=self.device) if self.training else None
         self.keep.append(amax)
-        self.call(self.fwd, lib.dml_maxpool3x3s2_fwd, z0.ptr, p0.ptr, amax.data_ptr() if amax is not None else None,
-                  B, z0.H, z0.W, 64, self.dt)
+        if fuse_stem:
+            p0 = self.new(B, Hp, Wp, 64)
+            self.call(self.fwd, lib.dml_bn_relu_maxpool3x3s2_fwd, stem.y.ptr, stem.scale.data_ptr(), stem.shift.data_ptr(),
+                      stem.mean.data_ptr(), p0.ptr, amax.data_ptr(), stem.mask.data_ptr(), None, 0, None, self.amax_of(p0),
+                      B, Hs, Ws, 64, stem.y.ld)
+        else:
+            z0 = stem.z
+            p0 = self.new(B, Hp, Wp, 64)
+            self.call(self.fwd, lib.dml_maxpool3x3s2_fwd, z0.ptr, p0.ptr, amax.data_ptr() if amax is not None else None,
+                      B, z0.H, z0.W, 64, self.dt)
 
         # bottlenecks (resnet.py:95-115)
         blocks = []
@@ -1255,10 +1340,13 @@ class Plan:
         for rec in reversed(blocks):
             self.block_bwd(rec)
         # max pool + stem
-        dz0 = self.grad_of(z0)
-        self.call(self.bwd, lib.dml_maxpool3x3s2_bwd, self.grad_of(p0).ptr, amax.data_ptr(), dz0.ptr, B, z0.H, z0.W,
-                  64, self.dt)
-        self.unit_bwd(stem, dz0, need_dgrad=False)
+        if fuse_stem:
+            self.stem_bwd_fused(stem, self.grad_of(p0), amax)
+        else:
+            dz0 = self.grad_of(z0)
+            self.call(self.bwd, lib.dml_maxpool3x3s2_bwd, self.grad_of(p0).ptr, amax.data_ptr(), dz0.ptr, B, z0.H, z0.W,
+                      64, self.dt)
+            self.unit_bwd(stem, dz0, need_dgrad=False)
         self.flush_wgrad()
         self.backbone_bwd_range = (backbone_start, len(self.bwd))
         for a, args, i in self.direct_planes:       # planes nobody reads (outputs that only feed resizes / concats): not written
@@ -1429,8 +1517,16 @@ class Plan:
                 self.call(self.bwd, lib.dml_unpad_wgrad, gb.data_ptr(), st.grad_ptr_of(fin.bias), 1, 1, K, Kp)
             self.mark_grad(fin.bias)
         self.conv_wgrad(ucls.z, de, fin, 256, pad_rows=Kp)
-        self.conv_dgrad(de, fin, wt_fin, ucls.z)
-        self.unit_bwd(ucls, self.grad_of(ucls.z))                       # -> d cat2
+        # f16x2 training: d(ucls.z) = de . W is a rank-K product -- the unit's two BatchNorm-backward passes form it from `de` (38 MB) and
+        # the conv's master weight instead of reading a 604 MB tensor twice that a data-gradient launch wrote
+        if (self.fuse_head_dgrad_on and self.f32_split == 2 and self.dtype == torch.float32 and not self.sync and self.h2_direct_on
+                and ucls.dtype == self.dtype and ucls.z is ucls.z.root and ucls.drop is None and (ucls.mask is not None or not ucls.relu)
+                and fin.kernel_size == (1, 1) and fin.stride == (1, 1) and fin.weight.dtype == torch.float32
+                and fin.in_channels == ucls.conv.out_channels and fin.in_channels % 8 == 0 and Kp in (8, 16, 24, 32)):
+            self.unit_bwd(ucls, None, dz_from=(de, fin.weight.data_ptr(), K))          # -> d cat2
+        else:
+            self.conv_dgrad(de, fin, wt_fin, ucls.z)
+            self.unit_bwd(ucls, self.grad_of(ucls.z))                   # -> d cat2
         dcat2 = self.grad_of(cat2)
         # upsample branch -> d(aspp output)
         dproj = self.grad_of(uproj.z)
