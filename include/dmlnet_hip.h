@@ -569,6 +569,30 @@ int dml_novel_relabel_multi(const float* feats, const float* logits, const float
  * B H W > 2^40.  Nothing is launched when a code is returned. */
 int dml_knn_cosine_score(const float* feats, float* score, int B, int C, int H, int W, int neighbor_size, void* stream);
 
+/* The paper's "EDS + MMSP" anomaly score of logits[B,K,H,W] fp32 (NCHW, contiguous) over the classes k_first <= k < K
+ * (k_first = 1: --exclude_back without a copy): the min-max normalised, clipped distance sum and the min-max normalised
+ * maximum softmax probability mixed through a sigmoid gate -- anomaly/eval_ood_traditional.py:302-305, :434-435 and
+ * :447-448 of the reference (Coefficient_map(dis_sum, 0.2), lamda = 50; overwritten there by a leftover `conf = dis_sum`
+ * at :450), and, with prob_logit = 1, clip = 1000, threshold = 0.3, the recipe test_embedding.py:366-369 keeps commented.
+ * Per image b, every minimum and maximum over that image alone:
+ *   s(p) = -(sum_k L_k(p)) + 0.0, set to clip where >= clip       m(p) = 1 / sum_k exp(L_k(p) - max_k L_k(p))   (prob_logit = 0)
+ *   d(p) = (s(p) - min s) / (max s - min s)                            = max_k L_k(p)                            (prob_logit = 1)
+ *   q(p) = (m(p) - min m) / (max m - min m)
+ *   c(p) = 1 / (1 + exp(slope * (d(p) - threshold)))              conf(p) = c(p) d(p) + (1 - c(p)) q(p)
+ * A constant s or m map normalises to 0/0 = NaN and conf is NaN on every pixel of that image, as numpy evaluates the
+ * reference's statements (K - k_first = 1 without prob_logit is such a case).  An exp that overflows gives c = +0 and
+ * conf = q.  work: 4 B + 2 B H W floats -- min s, max s, min m, max m per image, then the raw s and m maps.
+ * Three launches ordered by the stream: the ranges' initialisation; pass 1 reads every logit from memory once (K - k_first
+ * <= 16 keeps them in registers, more re-reads them from cache for the softmax denominator), writes s and m and reduces both
+ * ranges per wave, per workgroup and with at most one atomic pair per map per workgroup (an atomic that could not change the
+ * stored value is skipped); pass 2 reads the two maps and writes conf.
+ * 16-byte loads and stores (4 pixels per lane) when H W % 4 == 0 and the pointers are 16-byte aligned, one float per lane
+ * otherwise.  Atomic min / max do not depend on the order: bitwise reproducible, image b of a batch equals the image alone.
+ * DML_EINVAL: a NULL pointer, B, K, H, W <= 0, k_first < 0 or k_first >= K.  DML_EUNSUPPORTED: K - k_first > 32, B > 65535
+ * or B H W > 2^40.  Nothing is launched when a code is returned. */
+int dml_dissum_msp_score(const float* logits, float* conf, float* work, int B, int K, int H, int W, int k_first,
+                         float clip, float threshold, float slope, int prob_logit, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DML loss = CE(-dist^2)/n + alpha * VAR/n (anomaly/models/models.py:42-78; live part of
  * utils/loss.py:34-42 is alpha = 0).

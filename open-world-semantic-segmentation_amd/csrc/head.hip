@@ -799,6 +799,151 @@ __global__ __launch_bounds__(256) void minmax_norm_kernel(float* __restrict__ sc
     }
 }
 
+// ---- EDS + MMSP: the clipped distance sum and the maximum softmax probability (or the maximum logit), each min-max normalised
+// per image, mixed through a sigmoid gate on the first (anomaly/eval_ood_traditional.py:302-305,434-435,447-448 of the
+// reference; test_embedding.py:366-369 with prob_logit).  Pass 1 writes the raw maps s and m and leaves their ranges in
+// work[4 b .. 4 b + 3]; pass 2 normalises and mixes.  The signed-zero rule of atomic_min_f / atomic_max_f serves both ranges:
+// s is never -0.0 (the + 0.0f below), m can be (a maximum logit of -0.0).  PX = 4: a lane owns 4 consecutive pixels and reads
+// every plane with one 16-byte load.  REG keeps up to MIX_KREG planes in registers; beyond that the softmax denominator reads
+// the logits a second time, from cache (as argmax_msp_kernel does).  Both forms do the same operations in the same order.
+constexpr int MIX_MAXK = 32, MIX_KREG = 16;
+// workgroups of pass 1 per image: with every workgroup of a 720 x 1280 frame resident at once their atomics on the same four
+// words arrive together and cost more than the loads; fewer workgroups that loop, and mix_range_update, cut the call from
+// 0.058 to 0.032 ms there.  The form that re-reads wants more waves in flight.
+constexpr int MIX_GRID_REG = 512, MIX_GRID_REREAD = 2048;
+
+// One atomic pair at most: a stored minimum only falls and a stored maximum only rises while pass 1 runs, so a value read
+// beforehand -- however stale -- that already is at or beyond ours means the atomic could change nothing, and it is skipped.
+// Two zeros are ordered by their sign (see atomic_min_f), which a float comparison cannot see: they go to the atomic.
+__device__ __forceinline__ void mix_range_update(float* lohi, float lo, float hi) {
+    const volatile float* cur = lohi;
+    const float clo = cur[0], chi = cur[1];
+    if (!(clo <= lo) || (lo == 0.f && clo == 0.f)) atomic_min_f(lohi, lo);
+    if (!(chi >= hi) || (hi == 0.f && chi == 0.f)) atomic_max_f(lohi + 1, hi);
+}
+
+template <int PX> __device__ __forceinline__ void mix_load(const float* p, float (&v)[PX]) {
+    if constexpr (PX == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+template <int PX> __device__ __forceinline__ void mix_store(float* p, const float (&v)[PX]) {
+    if constexpr (PX == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+}
+
+template <int PX, bool REG>
+__global__ __launch_bounds__(256) void dissum_msp_maps_kernel(const float* __restrict__ logits, float* __restrict__ smap,
+                                                              float* __restrict__ mmap, float* work, int K, int k_first,
+                                                              int64_t HW, float clip, int prob_logit) {
+    __shared__ float sred[4][4];
+    const int b = blockIdx.y, Kn = K - k_first;
+    const float* img = logits + ((int64_t)b * K + k_first) * HW;
+    float slo = INFINITY, shi = -INFINITY, mlo = INFINITY, mhi = -INFINITY;
+    for (int64_t pix = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * PX; pix < HW;
+         pix += (int64_t)gridDim.x * blockDim.x * PX) {
+        const float* src = img + pix;
+        float sum[PX], best[PX], den[PX], s[PX], m[PX];
+#pragma unroll
+        for (int p = 0; p < PX; ++p) { sum[p] = 0.f; den[p] = 0.f; }
+        if constexpr (REG) {
+            float v[MIX_KREG][PX];
+#pragma unroll
+            for (int k = 0; k < MIX_KREG; ++k)
+                if (k < Kn) mix_load<PX>(src + (int64_t)k * HW, v[k]);
+#pragma unroll
+            for (int p = 0; p < PX; ++p) best[p] = v[0][p];
+#pragma unroll
+            for (int k = 0; k < MIX_KREG; ++k)
+                if (k < Kn) {
+#pragma unroll
+                    for (int p = 0; p < PX; ++p) { sum[p] += v[k][p]; best[p] = fmaxf(best[p], v[k][p]); }
+                }
+            if (!prob_logit) {
+#pragma unroll
+                for (int k = 0; k < MIX_KREG; ++k)
+                    if (k < Kn) {
+#pragma unroll
+                        for (int p = 0; p < PX; ++p) den[p] += expf(v[k][p] - best[p]);
+                    }
+            }
+        } else {
+            float v[PX];
+            mix_load<PX>(src, v);
+#pragma unroll
+            for (int p = 0; p < PX; ++p) best[p] = v[p];
+            for (int k = 0; k < Kn; ++k) {
+                mix_load<PX>(src + (int64_t)k * HW, v);
+#pragma unroll
+                for (int p = 0; p < PX; ++p) { sum[p] += v[p]; best[p] = fmaxf(best[p], v[p]); }
+            }
+            if (!prob_logit) {
+                for (int k = 0; k < Kn; ++k) {
+                    mix_load<PX>(src + (int64_t)k * HW, v);
+#pragma unroll
+                    for (int p = 0; p < PX; ++p) den[p] += expf(v[p] - best[p]);
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+            s[p] = -sum[p] + 0.0f;                                  // a zero sum scores +0.0, never -0.0
+            if (s[p] >= clip) s[p] = clip;
+            m[p] = prob_logit ? best[p] : 1.f / den[p];
+            slo = fminf(slo, s[p]); shi = fmaxf(shi, s[p]);
+            mlo = fminf(mlo, m[p]); mhi = fmaxf(mhi, m[p]);
+        }
+        mix_store<PX>(smap + (int64_t)b * HW + pix, s);
+        mix_store<PX>(mmap + (int64_t)b * HW + pix, m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        slo = fminf(slo, __shfl_xor(slo, o, 64)); shi = fmaxf(shi, __shfl_xor(shi, o, 64));
+        mlo = fminf(mlo, __shfl_xor(mlo, o, 64)); mhi = fmaxf(mhi, __shfl_xor(mhi, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        float* r = sred[threadIdx.x >> 6];
+        r[0] = slo; r[1] = shi; r[2] = mlo; r[3] = mhi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+            slo = fminf(slo, sred[w][0]); shi = fmaxf(shi, sred[w][1]);
+            mlo = fminf(mlo, sred[w][2]); mhi = fmaxf(mhi, sred[w][3]);
+        }
+        if (slo <= shi) mix_range_update(work + 4 * b, slo, shi);
+        if (mlo <= mhi) mix_range_update(work + 4 * b + 2, mlo, mhi);
+    }
+}
+
+// the gate is the plain division: an exp that overflows gives c = +0, 1 - c = 1 and conf = q
+template <int PX>
+__global__ __launch_bounds__(256) void dissum_msp_mix_kernel(const float* __restrict__ smap, const float* __restrict__ mmap,
+                                                             const float* __restrict__ work, float* __restrict__ conf,
+                                                             int64_t HW, float threshold, float slope) {
+    const int b = blockIdx.y;
+    const float slo = work[4 * b], sden = work[4 * b + 1] - slo;
+    const float mlo = work[4 * b + 2], mden = work[4 * b + 3] - mlo;
+    for (int64_t pix = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * PX; pix < HW;
+         pix += (int64_t)gridDim.x * blockDim.x * PX) {
+        const int64_t i = (int64_t)b * HW + pix;
+        float s[PX], m[PX], out[PX];
+        mix_load<PX>(smap + i, s);
+        mix_load<PX>(mmap + i, m);
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+            const float d = (s[p] - slo) / sden;
+            const float q = (m[p] - mlo) / mden;
+            const float c = 1.f / (1.f + expf(slope * (d - threshold)));
+            out[p] = c * d + (1.f - c) * q;
+        }
+        mix_store<PX>(conf + i, out);
+    }
+}
+
 __global__ __launch_bounds__(256) void novel_relabel_kernel(const float* __restrict__ feats,
                                                             const float* __restrict__ logits,
                                                             const float* __restrict__ proto,
@@ -1632,6 +1777,39 @@ extern "C" int dml_novel_relabel_multi(const float* feats, const float* logits, 
     if (N == 0) return 0;
     open_world_launch<false>(logits, feats, protos, new_labels, preds, nullptr, nullptr, nullptr, B, C, K, (int64_t)H * W,
                              N, thresh, vs_known, 0.f, 0, static_cast<hipStream_t>(stream));
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dml_dissum_msp_score(const float* logits, float* conf, float* work, int B, int K, int H, int W, int k_first,
+                                    float clip, float threshold, float slope, int prob_logit, void* stream) {
+    if (!logits || !conf || !work || B <= 0 || K <= 0 || H <= 0 || W <= 0 || k_first < 0 || k_first >= K) return DML_EINVAL;
+    if (K - k_first > MIX_MAXK || B > 65535) return DML_EUNSUPPORTED;
+    // the image index is the grid's y; 2^40 pixels keep every offset into the maps inside int64
+    if ((int64_t)H * W > (1ll << 40) / B) return DML_EUNSUPPORTED;
+    const int64_t HW = (int64_t)H * W;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float* smap = work + 4 * (int64_t)B;
+    float* mmap = smap + (int64_t)B * HW;
+    // with H W % 4 == 0 every plane, every image of the maps and the first class's plane keep the base pointer's alignment
+    const bool vec_maps = HW % 4 == 0 && aligned16(work);
+    const bool vec1 = vec_maps && aligned16(logits), vec2 = vec_maps && aligned16(conf);
+    const bool reg = K - k_first <= MIX_KREG;
+    hipLaunchKernelGGL(minmax_init_kernel, dim3((2 * B + 63) / 64), dim3(64), 0, st, work, 2 * B);
+    const dim3 grid1(grid_for(vec1 ? HW / 4 : HW, 256, reg ? MIX_GRID_REG : MIX_GRID_REREAD), B);
+    const dim3 grid2(grid_for(vec2 ? HW / 4 : HW, 256, 2048), B);
+#define MIX_MAPS(PX, REG)                                                                                              \
+    hipLaunchKernelGGL((dissum_msp_maps_kernel<PX, REG>), grid1, dim3(256), 0, st, logits, smap, mmap, work, K, k_first, \
+                       HW, clip, prob_logit)
+    if (vec1 && reg) MIX_MAPS(4, true);
+    else if (vec1) MIX_MAPS(4, false);
+    else if (reg) MIX_MAPS(1, true);
+    else MIX_MAPS(1, false);
+#undef MIX_MAPS
+    if (vec2)
+        hipLaunchKernelGGL(dissum_msp_mix_kernel<4>, grid2, dim3(256), 0, st, smap, mmap, work, conf, HW, threshold, slope);
+    else
+        hipLaunchKernelGGL(dissum_msp_mix_kernel<1>, grid2, dim3(256), 0, st, smap, mmap, work, conf, HW, threshold, slope);
     DML_LAUNCH_CHECK();
     return 0;
 }

@@ -97,6 +97,7 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_head_bwd_fused),
     DML_ENTRY(dml_argmax_msp),
     DML_ENTRY(dml_dissum_score),
+    DML_ENTRY(dml_dissum_msp_score),
     DML_ENTRY(dml_novel_relabel),
     DML_ENTRY(dml_open_world_post),
     DML_ENTRY(dml_novel_relabel_multi),

@@ -4,7 +4,11 @@
 
 Per frame: the resized copies go through `models.evaluate_multiscale` (the loop of :198-210, mean folded into the
 upsample kernel, scales concurrent), `pred = argmax` (:218), the confidence map of `--ood`
-(:275-340: msp | maxlogit | dissum | background, and :511-530: knn -- the sum, over the 8 x 8 pixels down-right and the
+(:275-340: msp | maxlogit | dissum | background; :302-305,434-435,447-448: dissum_msp -- the paper's "EDS + MMSP", the
+normalised distance sum d and the normalised maximum softmax q mixed as c d + (1 - c) q under the gate
+c = 1 / (1 + exp(mix_slope (d - mix_threshold))), which the reference computes on every dissum frame and then overwrites
+with a leftover `conf = dis_sum` at :450; one kernel pair, utils.dissum_msp_score, and no copy for --exclude_back;
+and :511-530: knn -- the sum, over the 8 x 8 pixels down-right and the
 8 x 8 pixels up-left of each pixel, of the cosine similarity between its embedding `ft1` and theirs, 0 beyond the image
 border: the reference's 128 rounds of zero-filled shifted copies in one kernel, utils.knn_cosine_score; its plt.figure /
 imshow / show calls and its resize of the map to segSize, the identity on a map that already has that size, are not
@@ -29,6 +33,9 @@ import models
 import utils
 
 IMG_SIZES, IMG_MAX_SIZE, PADDING_CONSTANT = (300, 375, 450, 525, 600), 1000, 8
+# the gate of `--ood dissum_msp`: the reference's Coefficient_map(dis_sum, 0.2) with lamda = 50 (:104-106,447); main() puts
+# --mix_threshold / --mix_slope here
+MIX = {"threshold": 0.2, "slope": 50.0}
 
 
 def resized_shapes(h, w):
@@ -39,12 +46,16 @@ def resized_shapes(h, w):
 
 
 def confidence(scores, ood, exclude_back=False, feats=None):
-    """:275-340, :511-530.  scores [1, K, H, W] on the device -> conf [H, W] on the device.  `knn` reads the embedding
-    feats [1, C, H, W] instead of the scores (the reference's `ft1`), so --exclude_back does not touch it."""
+    """:275-340, :434-448, :511-530.  scores [1, K, H, W] on the device -> conf [H, W] on the device.  `knn` reads the
+    embedding feats [1, C, H, W] instead of the scores (the reference's `ft1`), so --exclude_back does not touch it.
+    `dissum_msp` takes its gate from MIX and skips the background class inside the kernel."""
     if ood == "knn":
         if feats is None:
             raise ValueError("--ood knn scores the embedding: pass feats")
         return utils.knn_cosine_score(feats)[0]
+    if ood == "dissum_msp":
+        return utils.dissum_msp_score(scores, clip=400.0, threshold=MIX["threshold"], slope=MIX["slope"],
+                                      first_class=1 if exclude_back else 0)[0]
     tmp = scores[:, 1:].contiguous() if exclude_back else scores
     if ood == "msp":
         return utils.argmax_msp(tmp)[1][0]
@@ -141,9 +152,14 @@ def load_cfg(cfg_file, overrides):
     return cfg
 
 
-def main():
+def build_parser():
     p = argparse.ArgumentParser()
-    p.add_argument("--ood", default="dissum", choices=["msp", "maxlogit", "dissum", "background", "knn"])
+    p.add_argument("--ood", default="dissum", choices=["msp", "maxlogit", "dissum", "background", "knn",
+                                                           "dissum_msp"])
+    p.add_argument("--mix_threshold", type=float, default=MIX["threshold"],
+                   help="--ood dissum_msp: the normalised distance sum at which the gate is 1/2 (the reference's 0.2)")
+    p.add_argument("--mix_slope", type=float, default=MIX["slope"],
+                   help="--ood dissum_msp: the gate's steepness (the reference's lamda = 50)")
     p.add_argument("--exclude_back", action="store_true")
     p.add_argument("--out_label", type=int, default=13, help="cfg.OOD.out_labels: the anomaly id of StreetHazards")
     p.add_argument("--num_images", type=int, default=4)
@@ -159,7 +175,12 @@ def main():
     p.add_argument("--workers", type=int, default=0,
                    help="decode threads of the real-data run (default: min(16, CPUs this process may use))")
     p.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides (real-data run)")
-    opts = p.parse_args()
+    return p
+
+
+def main():
+    opts = build_parser().parse_args()
+    MIX.update(threshold=opts.mix_threshold, slope=opts.mix_slope)
     device = torch.device("cuda", opts.gpu)
     torch.cuda.set_device(device)
     torch.manual_seed(304)

@@ -1,5 +1,5 @@
 """Open-world scores computed on the device instead of on 134 MB/img host copies
-(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305,511-530)."""
+(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305,434-448,511-530)."""
 from __future__ import annotations
 
 import numpy as np
@@ -42,6 +42,32 @@ def dissum_score(logits: torch.Tensor, clip: float = 1000.0, inclusive: bool = F
     _lib.check(lib.dml_dissum_score(logits.data_ptr(), score.data_ptr(), work.data_ptr(), B, K, H, W, float(clip),
                                     1 if inclusive else 0, _st(logits)), "dml_dissum_score")
     return score
+
+
+def dissum_msp_score(logits: torch.Tensor, clip: float = 400.0, threshold: float = 0.2, slope: float = 50.0,
+                     prob: str = "softmax", first_class: int = 0) -> torch.Tensor:
+    """The paper's "EDS + MMSP" anomaly score of logits [B, K, H, W] over the classes first_class .. K - 1 -> [B, H, W]
+    (dml_dissum_msp_score): with d the clipped distance sum -sum_k logit_k and q the maximum softmax probability, each
+    min-max normalised per image, conf = c d + (1 - c) q under the gate c = 1 / (1 + exp(slope (d - threshold))) --
+    anomaly/eval_ood_traditional.py:302-305, :434-435 and :447-448 of the reference (the defaults are its clip 400,
+    Coefficient_map(dis_sum, 0.2) and lamda = 50).  first_class=1 is --exclude_back without a copy of the logits.
+    prob="logit" takes the maximum logit in place of the maximum softmax: the DeepLab driver's recipe
+    (test_embedding.py:366-369) is dissum_msp_score(outputs, clip=1000.0, threshold=0.3, prob="logit").  An image whose
+    d or q map is constant comes back NaN, as numpy evaluates the reference's statements."""
+    _need_cuda(logits)
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B, K, H, W]")
+    if prob not in ("softmax", "logit"):
+        raise ValueError("prob must be 'softmax' or 'logit', not %r" % (prob,))
+    lib = _lib.load()
+    logits = logits.contiguous().float()
+    B, K, H, W = logits.shape
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+    work = torch.empty(4 * B + 2 * B * H * W, dtype=torch.float32, device=logits.device)
+    _lib.check(lib.dml_dissum_msp_score(logits.data_ptr(), conf.data_ptr(), work.data_ptr(), B, K, H, W, int(first_class),
+                                        float(clip), float(threshold), float(slope), 1 if prob == "logit" else 0,
+                                        _st(logits)), "dml_dissum_msp_score")
+    return conf
 
 
 def knn_cosine_score(feats: torch.Tensor, neighbor_size: int = 9) -> torch.Tensor:
