@@ -13,6 +13,7 @@
 // BatchNorm + residual + ReLU (inference), bias, accumulate, and -- data gradient -- the BN-backward partial sums
 // of the tensor being written.
 #include "common.h"
+#include "conv_choice.h"
 #include <cstdlib>
 
 namespace {
@@ -38,7 +39,7 @@ struct ConvArgs {
     float* unused0_;             // unused0_ / unused1_: unused, they keep the layout and with it the kernels' code as it was
     uint32_t x_bytes, w_bytes;   // operand extents for the buffer descriptors (fast path: both < 2^31)
     int w_tiled;                 // weights in the tile-major layout (DmlConvDesc::w_tiled): LDS-DMA kernels only
-    int ws_min_tiles;            // DmlConvDesc::ws_min_tiles
+    int ws_min_tiles;            // DmlConvDesc::ws_min_tiles: host side only and read by no code (conv_choice.h looks at the descriptor)
     // f32_split == 2: operands as two fp16 planes of the power-of-two-scaled fp32 tensors (DmlConvDesc::x_planes ...)
     const void* x_planes;
     const void* w_planes;
@@ -63,8 +64,8 @@ struct ConvArgs {
     float* tail_ws;
     int* tail_cnt;
     int tail_full, tail_q;
-    int64_t tail_ws_elems_;      // host side only: capacities of the two buffers
-    int tail_cnt_len_;
+    int64_t tail_ws_elems_;      // host side only and read by no code: capacities of the two buffers (conv_choice.h looks at the
+    int tail_cnt_len_;           // descriptor)
     // data-gradient mode: masked residual gradient added in the epilogue (DmlConvDesc::res_*)
     const void* res_dz;
     const uint8_t* res_mask;
@@ -73,7 +74,7 @@ struct ConvArgs {
     const float* acc32;
     int acc32_ld;
     int f32_split;      // fp32 tensors: products through the three-term bf16 split (DmlConvDesc::f32_split)
-    // bit 0: the epilogue's bf16 output stores carry the non-temporal hint, bit 1: its partial-statistics stores (launch_conv)
+    // bit 0: the epilogue's bf16 output stores carry the non-temporal hint, bit 1: its partial-statistics stores (conv_choice.h)
     int nt_out;
     int unused1_;
     // one parity class of a stride-2 data gradient as a stride-1 launch on dY's grid (DmlConvDesc::sub_grid): the launch's rows are
@@ -2221,80 +2222,11 @@ __global__ __launch_bounds__((MW * NW + NLD) * 64) void conv_ws_kernel(const Con
     conv_ws_body<MW, NW, MODE, NLD, PL, MT, EPI>(a, x_bytes, w_bytes);
 }
 
-// The library's run-time switches, read once.  Tests select kernel families through them.
-//   DML_CONV_V1     set: bf16 launches on the register-staged kernel instead of the LDS-DMA ones
-//   DML_CONV_BM256  256-row tiles of the LDS-DMA kernel: 0 never, 1 the rule in launch_conv (default), 2 every eligible layer,
-//                   >= 64 the K threshold of the rule
-//   DML_CONV_WS     non-zero: bf16 launches on conv_ws_kernel wherever conv_ws_eligible allows (default 0)
-struct ConvSwitches {
-    bool v1;
-    int bm256, ws;
-};
-static const ConvSwitches& conv_switches() {
-    static const ConvSwitches s = {getenv("DML_CONV_V1") != nullptr, getenv("DML_CONV_BM256") ? atoi(getenv("DML_CONV_BM256")) : 1,
-                                   getenv("DML_CONV_WS") ? atoi(getenv("DML_CONV_WS")) : 0};
+// The library's run-time switches (conv_choice.h: ConvSwitches), read once: the library's one look at the environment.
+static const conv_choice::ConvSwitches& conv_switches() {
+    static const conv_choice::ConvSwitches s = {getenv("DML_CONV_V1") != nullptr, getenv("DML_CONV_BM256") ? atoi(getenv("DML_CONV_BM256")) : 1,
+                                                getenv("DML_CONV_WS") ? atoi(getenv("DML_CONV_WS")) : 0};
     return s;
-}
-
-// bytes of the activation / weight operands with ES-byte elements (operand extents of the buffer descriptors)
-static int64_t conv_x_bytes(const ConvArgs& a, const int es) { return (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * es; }
-static int64_t conv_w_bytes(const ConvArgs& a, const int es) { return (int64_t)a.N * a.Ktot * es; }
-
-// bf16: may this launch run on the LDS-DMA kernels?  K tiles inside one tap, N > 32, tensors addressable with a 31-bit byte offset
-// (shared by launch_conv and dml_conv_stat_rows)
-static bool conv_dma_eligible(const ConvArgs& a, const int64_t xb, const int64_t wb) {
-    return !conv_switches().v1 && (a.C % BK) == 0 && a.R * a.S <= 32 && a.N > 32 && xb < (1ll << 31) && wb < (1ll << 31);
-}
-
-// ... and among them on conv_ws_kernel?  (shared by launch_conv and dml_conv_stat_rows)
-static bool conv_ws_eligible(const ConvArgs& a, const int64_t xb, const int64_t wb) {
-    // bf16 plans: OPT-IN (DML_CONV_WS=1).  Per launch it wins where K is long (rule below), but in the train step the persistent
-    // 150 KB-of-LDS workgroups keep the side stream's weight-gradient workgroups off the CUs they hold and static tile lists
-    // cannot rebalance around them: whole step 391.5 / 392.2 images/s with it, 395.3 / 394.9 without (two interleaved pairs,
-    // profiles/r04_ab_ws.txt).  The two-plane fp32 mode (conv_ws_planes_eligible) always runs on it.
-    // (forward-only for the long-K launches, where nothing runs beside the main stream, measured +0.1...0.4 % on the step -- and moved
-    // the bf16 plan's rounding (48-row statistics groups) enough to redraw the chaotic 30-step trajectory of
-    // tests/test_gpu_training_equivalence.py past its bar; not worth a different default)
-    if ((!conv_switches().ws && a.ws_min_tiles <= 0) || !a.w_tiled || (a.C % BK) != 0 || a.R * a.S > 32 || (a.N % 128) != 0) return false;
-    if (xb >= (1ll << 31) || wb >= (1ll << 31)) return false;
-    // long K loops only: a consumer wave runs its tile's epilogue itself, with nothing of the same workgroup to cover it, and
-    // below ~32 K steps per tile that costs more than the K loop gains (tools/bench_ws.py, profiles/r04_bench_ws_2.txt: K = 256
-    // with four tiles per workgroup 42.5 vs 31.6 us, K = 512 120 vs 89; K = 1024 28.6 vs 32.0, K = 2304 52.9 vs 60.5, K = 4608
-    // 158 vs 207, K = 18432 284 vs 372).  ws_min_tiles > 0 (tests) lifts the rule.
-    if (a.ws_min_tiles <= 0 && a.R * a.S * a.C < 1024) return false;
-    // a persistent workgroup per CU: the tile list must fill most of the chip
-    const int bn = (a.N % 256) == 0 ? 256 : 128, bm = (a.N % 256) == 0 ? 144 : 288;
-    const int64_t ntiles = ((int64_t)a.M + bm - 1) / bm * (a.N / bn);
-    return ntiles >= (a.ws_min_tiles > 0 ? a.ws_min_tiles : 192);
-}
-// two planes, forward: 48 x 256 tiles instead of 144 x 256 for launches that leave most of the chip empty (launch_conv; also decides
-// the rows per statistics partial: dml_conv_stat_rows)
-static bool ws_planes_short(const ConvArgs& a, const int mode) {
-    return mode == 0 && (a.N % 256) == 0 && ((a.M + 143) / 144) * (a.N / 256) * 2 <= 256;
-}
-// rows of the GEMM per BatchNorm statistics partial of a two-plane FORWARD launch: the whole 144-row wave tile (ws_tile_stats) except on
-// the 48-row wave tiles (64 output channels, short tiles)
-static int ws_planes_stat_rows(const ConvArgs& a, const int mode) {
-    if (mode != 0) return 48;
-    return (a.N == 64 || ws_planes_short(a, mode)) ? 48 : 144;
-}
-// the same kernel on two fp16 planes per operand (fp32 tensors, f32_split == 2): every shape it can address -- the alternative
-// is the three-term split kernel at a third of its rate
-static bool conv_ws_planes_eligible(const ConvArgs& a, const int mode) {
-    if (mode == 0 && a.accum) return false;      // (an accumulating FORWARD launch: no plan issues one; the forward epilogue has no such path)
-    if (a.f32_split != 2 || !a.x_planes || !a.w_planes || !a.x_unscale || !a.w_unscale) return false;
-    // (N = 320: the decoder's data gradient.  N = 64 -- layer1's 3x3 and the 256 -> 64 1x1 -- runs the 288 x 128 configuration with
-    // half of every tile empty: zero weight rows through the descriptor's range check, no stores; still ahead of the three-term
-    // kernel those layers took before: whole step +0.4 %, two interleaved pairs)
-    if ((a.C % BK) != 0 || a.R * a.S > 32 || (a.N % 64) != 0) return false;
-    if (mode == 1 && a.Ktot < 2 * BK) return false;      // (conv_epilogue_rows_ops stages in the slots of a tile's last two K stages)
-    // whole 16-byte vectors of the fp32 output and of every epilogue operand (conv_epilogue_rows)
-    if ((a.ldy & 3) != 0 || (a.post_res != nullptr && (a.post_ldres & 3) != 0) ||
-        ((reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.post_res) | reinterpret_cast<uintptr_t>(a.bias) |
-          reinterpret_cast<uintptr_t>(a.post_scale) | reinterpret_cast<uintptr_t>(a.post_shift) |
-          reinterpret_cast<uintptr_t>(a.post_mean)) & 15) != 0)
-        return false;
-    return conv_x_bytes(a, 2) + a.x_plane_bytes < (1ll << 31) && conv_w_bytes(a, 2) + a.w_plane_bytes < (1ll << 31);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3511,274 +3443,44 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const ReduceGro
     }
 }
 
-// shared by dml_conv_wgrad (single job) and dml_conv_wgrad_group: may this job run on the 256 x 256-tile kernel?
-static bool wgrad_big_eligible(const DmlWgradDesc* d) {
-    if (!d || !d->x || !d->dy || !d->dw || d->dtype != DML_BF16) return false;
-    if (d->C % 8 || d->ldx % 8 || d->N % 8 || d->ldy % 8) return false;
-    const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
-    const int64_t Ktot = (int64_t)d->R * d->S * d->C;
-    const int64_t tiles = (M + BK - 1) / BK;
-    const int cm = d->Cm > 0 ? d->Cm : d->C;
-    if (cm > d->C) return false;
-    const int64_t plane = (int64_t)d->N * Ktot;
-    const int64_t xb64 = (((int64_t)(d->B * d->Hi) * d->Wi - 1) * d->ldx + d->C) * 2;
-    const int64_t yb64 = ((M - 1) * d->ldy + d->N) * 2;
-    return plane >= 65536 && d->N % 256 == 0 && (d->N / 256) * ((Ktot + 255) / 256) >= 4 && tiles >= 16 &&
-           xb64 < (1ll << 31) && yb64 < (1ll << 31) && (int64_t)(d->B + 1) * d->Hi * d->Wi < (1 << 24) && M < (1 << 24) &&
-           d->ldx < (1 << 22) && d->ldy < (1 << 22);
-}
+// ------------------------------------------------------------------------------------------------
+// Host side.  Which kernel takes a descriptor, with which tiling and grid, is decided in conv_choice.h (pure host code, testable
+// without a GPU); here the kernel arguments are filled from the descriptor plus that choice, and one switch launches.
+// ------------------------------------------------------------------------------------------------
+namespace cc = conv_choice;
+static_assert(cc::BK == BK && cc::NTHREADS == NTHREADS && cc::WS_MT == WS_MT && cc::WS_STAT_ROWS == WS_STAT_ROWS &&
+                  cc::WS_NLD == WS_PLANES_NLD && cc::WB_THREADS == WB_THREADS && cc::WGW_TN == WGW_TN && cc::WGW_TK == WGW_TK &&
+                  cc::WGW_NLD == WGW_NLD && cc::WG_MAX_JOBS == WG_MAX_JOBS,
+              "conv_choice.h describes the kernels of this file");
 
-static void fill_wgrad_args(WgradArgs& a, const DmlWgradDesc* d) {
-    a.x = d->x; a.dy = d->dy; a.dw = d->dw;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
-    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
-    a.M = d->B * d->Ho * d->Wo;
-    a.Ktot = d->R * d->S * d->C;
-    a.div_wo = make_fastdiv((uint32_t)d->Wo);
-    a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
-    a.div_c = make_fastdiv((uint32_t)d->C);
-}
-
-template <typename T, int MODE>
-int launch_conv(const ConvArgs& base, hipStream_t st) {
-    ConvArgs a = base;
-    const int64_t xb = conv_x_bytes(a, (int)sizeof(T)), wb = conv_w_bytes(a, (int)sizeof(T));
-    const bool small = xb < (1ll << 31) && wb < (1ll << 31);
-    a.x_bytes = small ? (uint32_t)xb : 0u;
-    a.w_bytes = small ? (uint32_t)wb : 0u;
-    const bool aligned = (a.C % BK) == 0 && a.R * a.S <= 32 && small;
-    a.nblk_m = (a.M + 127) / 128;
-    // non-temporal epilogue stores for outputs that do not fit the L2 anyway (st16); smaller ones are better left there for
-    // their consumer (1x1 1024 -> 256 at 48 x 48, 19 MB: 45.3 us plain, 46.9 non-temporal).  DML_CONV_NT: 0 never, 1 this
-    // rule (default), 2 always
-    constexpr int nt_mode = 1;
-    // the partial statistics (64 B per wave instruction) follow only where they are many: beside non-temporal outputs,
-    // 19 MB of plain partial stores bring the stalls back (192 x 192, 64 -> 256: 158 us, 126 with both non-temporal; all
-    // plain 141), while 4.7 MB do better plain (48 x 48, 256 -> 1024: 41.1 against 45.4 us)
-    const bool nt_y = nt_mode == 2 || (nt_mode == 1 && (int64_t)a.M * a.N * (int64_t)sizeof(T) >= (32ll << 20));
-    const bool nt_p = nt_y && (int64_t)((a.M + 63) / 64) * a.N * 8 >= (8ll << 20);
-    a.nt_out = (nt_y ? 1 : 0) | (nt_p ? 2 : 0);
-    if constexpr (sizeof(T) == 2) {
-        // LDS-DMA kernel: bf16, K tiles inside one tap, tensors addressable with a 31-bit byte offset.  With a 3-stage
-        // ring (48 KB of LDS) and the 168-register budget three workgroups fit a CU like the register-staged kernel, and
-        // it is the default for every eligible shape: whole train step 362.4 vs 356.4 images/s (three interleaved A/B
-        // runs; a 4-stage ring on the largest grids only: 360.2).  In isolation the two kernels are within +-5 % of each
-        // other (tools/bench_conv.py); the register-staged kernel stays for fp32, unaligned channel counts (stem, final
-        // conv) and N <= 32.
-        if (conv_dma_eligible(a, xb, wb)) {
-            // wave-specialised kernel (conv_ws_kernel): one persistent workgroup per CU on 144-row tiles, tile-major weights,
-            // N a multiple of 128, enough tiles to fill the chip.  Same-box microbenchmarks against the ring kernel below
-            // (profiles/r04_ws_probe_3.txt vs r04_ws_probe_1_shipped.txt): layer3 3x3 67.5 -> 43.6 us, 1x1 1024 -> 256
-            // 37.6 -> 24.2, 1x1 256 -> 1024 38.4 -> 31.0, ASPP 3x3 385 -> 325-357, decoder 3x3 886 -> 825-870.
-            if (conv_ws_eligible(a, xb, wb)) {
-                constexpr int CUS = 256, NLD = 3;
-                const bool wide = (a.N % 256) == 0;
-                const int bm = wide ? 144 : 288;
-                a.nblk_m = (a.M + bm - 1) / bm;
-                a.nblk_n = a.N / (wide ? 256 : 128);
-                const int ntiles = a.nblk_m * a.nblk_n;
-                const int grid = ntiles < CUS ? ntiles : CUS;
-                if (wide)
-                    hipLaunchKernelGGL((conv_ws_kernel<1, 4, MODE, NLD>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, (uint32_t)xb,
-                                       (uint32_t)wb);
-                else
-                    hipLaunchKernelGGL((conv_ws_kernel<2, 2, MODE, NLD>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, (uint32_t)xb,
-                                       (uint32_t)wb);
-                DML_LAUNCH_CHECK();
-                return 0;
-            }
-            // grids that leave most of the chip idle (batch-1 inference, the anomaly model's down-scaled inputs): halve the
-            // tile width to double the workgroup count; per-FLOP the 128 x 64 tile is 15-25 % slower, so only below 200
-            // workgroups (1024 x 2048 bs 1: 235 -> 250 images/s, 5-scale open-set evaluation 92 -> 97.5 frames/s; the
-            // training grids are all larger)
-            const bool narrow = a.nblk_m * ((a.N + 127) / 128) < 200;
-            // tiles of the partially filled last round, split along K (DmlConvDesc::tail_*): when the remainder is at most
-            // half a round of the CUs, q = CUs / remainder parts per tile give every CU the same share
-            a.tail_full = 0;
-            a.tail_q = 1;
-            if (a.tail_ws != nullptr && a.N > 64 && !narrow) {
-                constexpr int CUS = 256;
-                const int ntiles = a.nblk_m * ((a.N + 127) / 128), full = ntiles / CUS * CUS, rem = ntiles - full;
-                if (full >= CUS && full <= 6 * CUS && rem > 0 && rem <= CUS / 2) {
-                    int q = CUS / rem;
-                    if (q > 8) q = 8;
-                    const int KTall = a.Ktot / BK;
-                    while (q > 1 && KTall / q < 6) --q;
-                    if (q > 1 && (int64_t)rem * q * 128 * 128 <= base.tail_ws_elems_ && rem <= base.tail_cnt_len_) {
-                        a.tail_full = full;
-                        a.tail_q = q;
-                    }
-                }
-            }
-            // 256-row tiles pay where the K loop is long (3x3 convolutions over >= 256 channels: layer4 / ASPP / decoder),
-            // with the K-split tail balancing their few tiles: in isolation ASPP 3x3 389 -> 343 us (1014 TFLOP/s), layer4
-            // 3x3 202 -> 176 us, decoder 3x3 1003 -> 922 us.  On the short-K 1x1 layers three
-            // workgroups of four waves hide latency better than two of eight (whole step -1.8 % with 256-row tiles
-            // everywhere).  DML_CONV_BM256: 0 = never, 1 = this rule (default), 2 = every eligible layer,
-            // >= 64 = the K threshold of the rule
-            // In the plan (serial profile, r02 v3 -> v5): ASPP forward 1.14 -> 0.98 ms, ASPP data gradients 1.12 -> 1.01,
-            // decoder forward 0.95 -> 0.86, layer4 3x3 -0.05; but layer3's 3x3 (K = 2304, only 288 tiles of 256 rows) LOSES
-            // 0.24 ms over its 44 launches -- one 72-step tile per CU at two waves per SIMD -- hence the tile-count clause.
-            const int bm256 = conv_switches().bm256;
-            const int tiles256 = ((a.M + 255) / 256) * (a.N / 128);
-            const bool long_k = bm256 >= 64 ? a.Ktot >= bm256 : (a.Ktot >= 4608 || (a.Ktot >= 2304 && tiles256 >= 512));
-            // The 256-row tile runs as 4 waves on 128 x 64 WAVE tiles (conv_igemm_dma_kernel<..., 256, 128>: 32 MFMAs per wave and
-            // K step against 12 KB of fragment reads, half the barriers per FLOP); the 8-wave variant on 64 x 64 wave tiles it
-            // replaced in round 3 (decoder 3x3 data gradient 1.064 -> 0.957 ms, whole step 385.3 -> 388.3 images/s) is gone.
-            if ((bm256 == 2 || (bm256 != 0 && long_k)) && a.N >= 128 && !narrow && a.N % 128 == 0) {
-                // 256-row tiles: whole tiles on the first multiple of 256 workgroups, the remainder split along K
-                constexpr int CUS = 256;
-                a.nblk_m = (a.M + 255) / 256;
-                a.nblk_n = a.N / 128;
-                const int ntiles = a.nblk_m * a.nblk_n, full = ntiles / CUS * CUS, rem = ntiles - full;
-                a.tail_full = 0;
-                a.tail_q = 1;
-                if (base.tail_ws != nullptr && full >= CUS && rem > 0 && rem <= CUS / 2) {
-                    int q = CUS / rem;
-                    if (q > 8) q = 8;
-                    const int KTall = a.Ktot / BK;
-                    while (q > 1 && KTall / q < 6) --q;
-                    if (q > 1 && (int64_t)rem * q * 256 * 128 <= base.tail_ws_elems_ && rem <= base.tail_cnt_len_) {
-                        a.tail_full = full;
-                        a.tail_q = q;
-                    }
-                }
-                const int grid = a.tail_q > 1 ? a.tail_full + (ntiles - a.tail_full) * a.tail_q : ntiles;
-                hipLaunchKernelGGL((conv_igemm_dma_kernel<128, MODE, 3, 2, 256, 128>), dim3(grid), dim3(256), 0, st, a, (uint32_t)xb,
-                                   (uint32_t)wb);
-                DML_LAUNCH_CHECK();
-                return 0;
-            }
-            if (a.tail_q > 1) {
-                a.nblk_n = (a.N + 127) / 128;
-                const int ntiles = a.nblk_m * a.nblk_n;
-                hipLaunchKernelGGL((conv_igemm_dma_kernel<128, MODE, 3>), dim3(a.tail_full + (ntiles - a.tail_full) * a.tail_q),
-                                   dim3(NTHREADS), 0, st, a, (uint32_t)xb, (uint32_t)wb);
-            } else if (a.N > 64 && !narrow) {
-                a.nblk_n = (a.N + 127) / 128;
-                hipLaunchKernelGGL((conv_igemm_dma_kernel<128, MODE, 3>), dim3(a.nblk_m * a.nblk_n), dim3(NTHREADS), 0, st, a,
-                                   (uint32_t)xb, (uint32_t)wb);
-            } else {
-                a.nblk_n = (a.N + 63) / 64;
-                hipLaunchKernelGGL((conv_igemm_dma_kernel<64, MODE, 3>), dim3(a.nblk_m * a.nblk_n), dim3(NTHREADS), 0, st, a,
-                                   (uint32_t)xb, (uint32_t)wb);
-            }
-            DML_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (a.w_tiled) return DML_EUNSUPPORTED;      // tile-major weights: only the LDS-DMA kernels above read them
-    if constexpr (sizeof(T) == 4 && MODE != 2) {
-        if (conv_ws_planes_eligible(a, MODE)) {
-            // fp32 tensors, products of two fp16 planes per operand on the matrix cores (DmlConvDesc.x_planes ...)
-            constexpr int CUS = 256, NLD = WS_PLANES_NLD;
-            const bool wide = (a.N % 256) == 0;
-            // 64 output channels (layer1's 3x3, the 256 -> 64 1x1, the data gradients of the 64 -> 256 1x1): 192 x 64 tiles on four
-            // 48 x 64 wave tiles.  On the 288 x 128 configuration half of every tile -- MFMAs and DMA pieces -- was empty
-            // (r04: 0.16-0.17 of the class's own bound).  Same box, old -> new: 3x3 64 -> 64 at 192 x 192 forward 347 -> 286 us, 1x1
-            // 256 -> 64 244 -> 185, 1x1 128 -> 64 190 -> 132; whole step +0.8 % (profiles/r05_ab_n64.txt)
-            const bool n64 = a.N == 64;
-            // Forward launches that leave most of the chip empty on 144-row tiles (batch-1 inference at 1024 x 2048: 57 row blocks on
-            // layer3 / layer4 / ASPP; the small maps of the tests): 48 x 256 tiles -- three times the workgroups, each with a third
-            // of the MFMAs per K step behind the same weight pieces.  (Round 6; 1024 x 2048 batch 1: see profiles/r06_infer_short_tiles.txt)
-            const bool shortm = ws_planes_short(a, MODE);
-            const int bm = wide ? (shortm ? 48 : 144) : (n64 ? 192 : 288);
-            a.nblk_m = (a.M + bm - 1) / bm;
-            a.nblk_n = wide ? a.N / 256 : (n64 ? 1 : (a.N + 127) / 128);      // (a last 128-wide block may be half empty: zero rows, no stores)
-            const int ntiles = a.nblk_m * a.nblk_n;
-            const int grid = ntiles < CUS ? ntiles : CUS;
-            const uint32_t xpb = (uint32_t)conv_x_bytes(a, 2), wpb = (uint32_t)conv_w_bytes(a, 2);
-            auto go = [&](auto epi_c) {
-                constexpr int EPI = decltype(epi_c)::value;
-                if (shortm) {
-                    if constexpr (MODE == 0 && EPI == 0)
-                        hipLaunchKernelGGL((conv_ws_kernel<1, 4, 0, NLD, 2, 3, 0>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, xpb, wpb);
-                } else if (n64)
-                    hipLaunchKernelGGL((conv_ws_kernel<4, 1, MODE, NLD, 2, 3, EPI>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, xpb, wpb);
-                else if (wide)
-                    hipLaunchKernelGGL((conv_ws_kernel<1, 4, MODE, NLD, 2, WS_MT, EPI>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, xpb, wpb);
-                else
-                    hipLaunchKernelGGL((conv_ws_kernel<2, 2, MODE, NLD, 2, WS_MT, EPI>), dim3(grid), dim3((4 + NLD) * 64), 0, st, a, xpb, wpb);
-            };
-            // data gradients: one instantiation per set of epilogue operands (conv_epilogue_rows_ops)
-            const int epi = MODE == 1 ? ((a.accum != 0 || a.res_dz != nullptr) ? 1 : 0) | (a.bnr_partials != nullptr ? 2 : 0) : 0;
-            if constexpr (MODE == 1) {
-                if (epi == 3) go(std::integral_constant<int, 3>{});
-                else if (epi == 2) go(std::integral_constant<int, 2>{});
-                else if (epi == 1) go(std::integral_constant<int, 1>{});
-                else go(std::integral_constant<int, 0>{});
-            } else {
-                go(std::integral_constant<int, 0>{});
-            }
-            DML_LAUNCH_CHECK();
-            return 0;
-        }
-        if (a.f32_split && aligned && a.N > 32) {      // (f32_split == 2 launches the planes kernel did not take: three-term split)
-            if (a.N > 64) {
-                a.nblk_n = (a.N + 127) / 128;
-                hipLaunchKernelGGL((conv_igemm_x3_kernel<128, MODE>), dim3(a.nblk_m * a.nblk_n), dim3(NTHREADS), 0, st, a);
-            } else {
-                a.nblk_n = (a.N + 63) / 64;
-                hipLaunchKernelGGL((conv_igemm_x3_kernel<64, MODE>), dim3(a.nblk_m * a.nblk_n), dim3(NTHREADS), 0, st, a);
-            }
-            DML_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if constexpr (MODE == 2) {
-        return DML_EUNSUPPORTED;      // acc32: LDS-DMA kernels only (bf16, C % 32 == 0, N > 32)
-    } else {
-        auto go = [&](auto bn_tag, auto al_tag) {
-            constexpr int BN = decltype(bn_tag)::value;
-            constexpr bool AL = decltype(al_tag)::value;
-            a.nblk_n = (a.N + BN - 1) / BN;
-            const int grid = a.nblk_m * a.nblk_n;
-            hipLaunchKernelGGL((conv_igemm_kernel<T, BN, AL, MODE>), dim3(grid), dim3(NTHREADS), 0, st, a);
-        };
-        using I128 = std::integral_constant<int, 128>;
-        using I64 = std::integral_constant<int, 64>;
-        using I32 = std::integral_constant<int, 32>;
-        const int bn = a.N > 64 ? 128 : (a.N > 32 ? 64 : 32);
-        if (aligned) {
-            if (bn == 128) go(I128{}, std::true_type{});
-            else if (bn == 64) go(I64{}, std::true_type{});
-            else go(I32{}, std::true_type{});
-        } else {
-            if (bn == 128) go(I128{}, std::false_type{});
-            else if (bn == 64) go(I64{}, std::false_type{});
-            else go(I32{}, std::false_type{});
-        }
-        DML_LAUNCH_CHECK();
-        return 0;
-    }
-}
-
-// The launch a descriptor describes, before launch_conv picks its kernel: every field of the descriptor that is in effect, the rest
-// zero.  Shared by dml_conv_igemm, which validates the descriptor first, and dml_conv_stat_rows, so that both see the same arguments.
-static ConvArgs conv_args(const DmlConvDesc* d) {
+// The kernel arguments of a launch: every field of the descriptor that is in effect, the rest zero, and the chosen tiling.
+static ConvArgs conv_args(const DmlConvDesc* d, const cc::ConvChoice& c) {
     ConvArgs a{};
     a.x = d->x; a.w = d->w; a.y = d->y; a.bias = d->bias; a.stats = d->stats;
     a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
     a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
-    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad; a.pad_x = d->pad_w_set ? d->pad_w : d->pad;
-    a.M = d->B * d->Ho * d->Wo;
-    a.Ktot = d->R * d->S * d->C;
+    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad; a.pad_x = cc::conv_pad_x(*d);
+    a.M = cc::conv_m(*d);
+    a.Ktot = cc::conv_ktot(*d);
     a.y_f32 = d->y_f32; a.accum = d->accum;
+    a.nblk_m = c.nblk_m; a.nblk_n = c.nblk_n;
     a.div_wo = make_fastdiv((uint32_t)d->Wo);
     a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
     a.div_c = make_fastdiv((uint32_t)d->C);
+    a.x_bytes = c.x_bytes; a.w_bytes = c.w_bytes;
     a.w_tiled = d->w_tiled ? 1 : 0;
-    a.ws_min_tiles = d->ws_min_tiles;
-    a.f32_split = d->dtype == DML_F32 ? d->f32_split : 0;
-    if (a.f32_split == 2 && d->x_planes && d->w_planes) {
+    a.f32_split = cc::conv_f32_split(*d);
+    if (cc::conv_has_planes(*d)) {
         a.x_planes = d->x_planes; a.w_planes = d->w_planes; a.x_unscale = d->x_unscale; a.w_unscale = d->w_unscale;
         a.x_plane_bytes = (uint32_t)(d->x_plane_stride * 2); a.w_plane_bytes = (uint32_t)(d->w_plane_stride * 2);
     }
     if (d->acc32) { a.acc32 = d->acc32; a.acc32_ld = d->acc32_ld; }
     if (d->res_dz) { a.res_dz = d->res_dz; a.res_mask = d->res_mask; a.res_ld = d->res_ld; }
-    a.tail_q = 1;
-    if (d->tail_ws && d->tail_counters && d->tail_ws_elems > 0 && d->tail_counters_len > 0) {
+    a.tail_full = c.tail_full; a.tail_q = c.tail_q;
+    // ws_min_tiles, tail_ws_elems_, tail_cnt_len_: read by nobody (conv_choice.h looks at the descriptor); set so that the argument block
+    // of a launch holds defined values in every member
+    a.ws_min_tiles = d->ws_min_tiles;
+    if (cc::conv_has_tail(*d)) {
         a.tail_ws = d->tail_ws; a.tail_cnt = d->tail_counters;
         a.tail_ws_elems_ = d->tail_ws_elems; a.tail_cnt_len_ = d->tail_counters_len;
     }
@@ -3792,8 +3494,94 @@ static ConvArgs conv_args(const DmlConvDesc* d) {
         if (d->dtype == DML_F32) a.bnr_gmax = d->bnr_gmax;
         a.bnr_inc = d->bnr_inc != 0 ? 1 : 0;
     }
+    a.nt_out = c.nt_out;
     if (d->sub_grid) { a.sub_grid = 1; a.sub_y = d->sub_y; a.sub_x = d->sub_x; }
     return a;
+}
+
+// two-plane instantiations of the wave-specialised kernel (ConvChoice::pl == 2)
+template <int MODE, int EPI>
+void launch_ws_planes(const cc::ConvChoice& c, const ConvArgs& a, hipStream_t st) {
+    constexpr int NLD = WS_PLANES_NLD;
+    const dim3 grid(c.grid), block(c.block);
+    if (c.mw == 1 && c.mt == 3) {      // 48 x 256 tiles: forward launches only
+        if constexpr (MODE == 0 && EPI == 0)
+            hipLaunchKernelGGL((conv_ws_kernel<1, 4, 0, NLD, 2, 3, 0>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+    } else if (c.mw == 4)
+        hipLaunchKernelGGL((conv_ws_kernel<4, 1, MODE, NLD, 2, 3, EPI>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+    else if (c.mw == 1)
+        hipLaunchKernelGGL((conv_ws_kernel<1, 4, MODE, NLD, 2, WS_MT, EPI>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+    else
+        hipLaunchKernelGGL((conv_ws_kernel<2, 2, MODE, NLD, 2, WS_MT, EPI>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+}
+
+template <typename T, int MODE>
+void launch_conv(const cc::ConvChoice& c, const ConvArgs& a, hipStream_t st) {
+    const dim3 grid(c.grid), block(c.block);
+    switch (c.family) {
+    case cc::CONV_RING:
+        if constexpr (sizeof(T) == 2) {
+            if (c.bm == 256)
+                hipLaunchKernelGGL((conv_igemm_dma_kernel<128, MODE, 3, 2, 256, 128>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+            else if (c.bn == 128)
+                hipLaunchKernelGGL((conv_igemm_dma_kernel<128, MODE, 3>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+            else
+                hipLaunchKernelGGL((conv_igemm_dma_kernel<64, MODE, 3>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+        }
+        break;
+    case cc::CONV_WS:
+        if constexpr (sizeof(T) == 2) {
+            if (c.mw == 1)
+                hipLaunchKernelGGL((conv_ws_kernel<1, 4, MODE, cc::WS_NLD>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+            else
+                hipLaunchKernelGGL((conv_ws_kernel<2, 2, MODE, cc::WS_NLD>), grid, block, 0, st, a, c.kx_bytes, c.kw_bytes);
+        } else if constexpr (MODE == 1) {
+            // data gradients: one instantiation per set of epilogue operands (conv_epilogue_rows_ops)
+            if (c.epi == 3) launch_ws_planes<1, 3>(c, a, st);
+            else if (c.epi == 2) launch_ws_planes<1, 2>(c, a, st);
+            else if (c.epi == 1) launch_ws_planes<1, 1>(c, a, st);
+            else launch_ws_planes<1, 0>(c, a, st);
+        } else if constexpr (MODE == 0) {
+            launch_ws_planes<0, 0>(c, a, st);
+        }
+        break;
+    case cc::CONV_X3:
+        if constexpr (sizeof(T) == 4 && MODE != 2) {
+            if (c.bn == 128) hipLaunchKernelGGL((conv_igemm_x3_kernel<128, MODE>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((conv_igemm_x3_kernel<64, MODE>), grid, block, 0, st, a);
+        }
+        break;
+    default:
+        if constexpr (MODE != 2) {
+            if (c.aligned) {
+                if (c.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, true, MODE>), grid, block, 0, st, a);
+                else if (c.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, true, MODE>), grid, block, 0, st, a);
+                else hipLaunchKernelGGL((conv_igemm_kernel<T, 32, true, MODE>), grid, block, 0, st, a);
+            } else {
+                if (c.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, false, MODE>), grid, block, 0, st, a);
+                else if (c.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, false, MODE>), grid, block, 0, st, a);
+                else hipLaunchKernelGGL((conv_igemm_kernel<T, 32, false, MODE>), grid, block, 0, st, a);
+            }
+        }
+        break;
+    }
+}
+
+// everything of WgradArgs but the tiling (nblk_n, nblk_k, slab_tiles) and the workspace
+static void fill_wgrad_args(WgradArgs& a, const DmlWgradDesc* d, const bool planes) {
+    a.x = d->x; a.dy = d->dy; a.dw = d->dw;
+    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
+    a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
+    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
+    a.M = d->B * d->Ho * d->Wo;
+    a.Ktot = d->R * d->S * d->C;
+    a.div_wo = make_fastdiv((uint32_t)d->Wo);
+    a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
+    a.div_c = make_fastdiv((uint32_t)d->C);
+    a.x_planes = planes ? d->x_planes : nullptr; a.dy_planes = planes ? d->dy_planes : nullptr;
+    a.x_unscale = planes ? d->x_unscale : nullptr; a.dy_unscale = planes ? d->dy_unscale : nullptr;
+    a.x_plane_bytes = planes ? (uint32_t)(d->x_plane_stride * 2) : 0u;
+    a.dy_plane_bytes = planes ? (uint32_t)(d->dy_plane_stride * 2) : 0u;
 }
 
 }  // namespace
@@ -3802,397 +3590,99 @@ static ConvArgs conv_args(const DmlConvDesc* d) {
 // wave-specialised kernel takes it, DML_STAT_ROWS otherwise.  The caller sizes the partial buffers with it and passes it on to
 // dml_bn_finalize_rows / dml_bn_moments_rows (the BN-backward finalize only needs the group count).
 extern "C" int dml_conv_stat_rows(const DmlConvDesc* d) {
-    if (!d) return DML_STAT_ROWS;
-    const ConvArgs a = conv_args(d);
-    if (d->dtype == DML_F32)      // (plane strides dml_conv_igemm accepts: a larger one would wrap in x_plane_bytes)
-        return (d->x_plane_stride < (1ll << 30) && d->w_plane_stride < (1ll << 30) && conv_ws_planes_eligible(a, d->mode))
-                   ? ws_planes_stat_rows(a, d->mode) : DML_STAT_ROWS;
-    if (d->dtype != DML_BF16) return DML_STAT_ROWS;
-    const int64_t xb = conv_x_bytes(a, 2), wb = conv_w_bytes(a, 2);
-    return (conv_dma_eligible(a, xb, wb) && conv_ws_eligible(a, xb, wb)) ? WS_STAT_ROWS : DML_STAT_ROWS;
+    cc::ConvChoice c;
+    cc::conv_choose(d, conv_switches(), &c);
+    return c.stat_rows;
 }
 
 extern "C" int dml_conv_igemm(const DmlConvDesc* d, void* stream) {
-    if (!d || !d->x || !d->w || !d->y) return DML_EINVAL;
-    if (d->dtype != DML_F32 && d->dtype != DML_BF16) return DML_EINVAL;
-    const int vec = d->dtype == DML_BF16 ? 8 : 4;
-    if (d->C % vec || d->ldx % vec) return DML_EALIGN;
-    if (d->mode != 0 && d->mode != 1) return DML_EINVAL;
-    if (d->mode == 1 && d->stride != 1 && d->stride != 2) return DML_EUNSUPPORTED;
-    if (d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->N <= 0 || d->R <= 0 || d->S <= 0) return DML_EINVAL;
-    if ((int64_t)d->B * d->Ho * d->Wo >= (1ll << 31)) return DML_EINVAL;
-    if (d->stats && d->bias) return DML_EINVAL;
-    const ConvArgs a = conv_args(d);
-    if (a.f32_split < 0 || a.f32_split > 2) return DML_EINVAL;
-    if (a.x_planes) {
-        if (!d->x_unscale || !d->w_unscale || d->x_plane_stride <= 0 || d->w_plane_stride <= 0 ||
-            d->x_plane_stride >= (1ll << 30) || d->w_plane_stride >= (1ll << 30))
-            return DML_EINVAL;
-        if ((reinterpret_cast<uintptr_t>(d->x_planes) & 15) || (reinterpret_cast<uintptr_t>(d->w_planes) & 15) ||
-            (d->x_plane_stride & 7) || (d->w_plane_stride & 7))
-            return DML_EALIGN;
-    }
-    if (d->w_tiled && (d->dtype != DML_BF16 || d->C % BK || d->N % 64)) return DML_EUNSUPPORTED;
-    if (d->acc32) {
-        // fp32 staging of a gradient with several producers: the 16-byte-vector bf16 path of the data gradient only
-        if (d->mode != 1 || d->dtype != DML_BF16 || d->y_f32 || d->accum || d->res_dz || d->bnr_partials) return DML_EINVAL;
-        if (d->N % 8 || d->ldy % 8 || d->acc32_ld % 4 || (reinterpret_cast<uintptr_t>(d->y) & 15) ||
-            (reinterpret_cast<uintptr_t>(d->acc32) & 15) || d->N <= 32)
-            return DML_EALIGN;
-    }
-    if (d->res_dz) {
-        // masked residual gradient in the epilogue: the 16-byte-vector bf16 path of the data gradient only
-        // (fp32: the two-plane kernel's row epilogue, 4-channel mask bytes; checked against the launch below)
-        if (d->mode != 1 || d->y_f32 || d->accum || !d->res_mask) return DML_EINVAL;
-        if (d->dtype == DML_BF16) {
-            if (d->N % 8 || d->ldy % 8 || d->res_ld % 8 || (reinterpret_cast<uintptr_t>(d->y) & 15) ||
-                (reinterpret_cast<uintptr_t>(d->res_dz) & 15) || d->N <= 32)
-                return DML_EALIGN;
-            if ((d->N & 63) == 0 && (reinterpret_cast<uintptr_t>(d->res_mask) & 7)) return DML_EALIGN;      // 8-byte mask rows
-        } else if (d->N % 64 || d->res_ld % 4 || ((reinterpret_cast<uintptr_t>(d->res_dz) | reinterpret_cast<uintptr_t>(d->res_mask)) & 15)) {
-            return DML_EALIGN;      // (16 mask bytes per pixel row and 64 channels are one load)
-        }
-    }
-    if (a.tail_ws && (reinterpret_cast<uintptr_t>(a.tail_ws) & 15)) return DML_EALIGN;
-    if (d->post_scale) {
-        if (d->mode != 0 || !d->post_shift || !d->post_mean || d->stats || d->bias || d->accum || d->y_f32) return DML_EINVAL;
-        if (d->post_res && (d->post_ldres % vec || (reinterpret_cast<uintptr_t>(d->post_res) & 15))) return DML_EALIGN;
-    }
-    if (d->bnr_partials) {
-        // fused BN-backward reduce: data-gradient mode; bf16 result stored as 16-byte vectors, 8-channel mask bytes -- or fp32 on the
-        // two-plane kernel (checked below, once the launch is described), 4-channel mask bytes
-        if (d->mode != 1 || d->y_f32 || !d->bnr_y || !d->bnr_mean || !d->bnr_invstd || (d->bnr_relu && !d->bnr_mask))
-            return DML_EINVAL;
-        if (d->dtype == DML_BF16) {
-            if (d->N % 8 || d->ldy % 8 || d->bnr_ldy % 8 || (reinterpret_cast<uintptr_t>(d->y) & 15) ||
-                (reinterpret_cast<uintptr_t>(d->bnr_y) & 15) || (reinterpret_cast<uintptr_t>(d->bnr_partials) & 15) || d->N <= 32)
-                return DML_EUNSUPPORTED;
-            if (d->bnr_relu && (d->N & 63) == 0 && (reinterpret_cast<uintptr_t>(d->bnr_mask) & 7)) return DML_EALIGN;
-        } else {
-            if (d->N % 64 || d->bnr_ldy % 4) return DML_EUNSUPPORTED;
-            if (((reinterpret_cast<uintptr_t>(d->bnr_y) | reinterpret_cast<uintptr_t>(d->bnr_partials) |
-                  reinterpret_cast<uintptr_t>(d->bnr_mean) | reinterpret_cast<uintptr_t>(d->bnr_invstd) |
-                  (d->bnr_relu ? reinterpret_cast<uintptr_t>(d->bnr_mask) : 0)) & 15) != 0)
-                return DML_EALIGN;
-        }
-    }
-    // (only the two-plane row epilogue with both operand sets knows the increment: an accumulating fp32 launch)
-    if (a.bnr_inc && (!d->accum || d->dtype != DML_F32 || d->res_dz)) return DML_EUNSUPPORTED;
-    if (d->sub_grid) {
-        // a parity class of a stride-2 data gradient: stride-1 geometry on dY's grid, the two-plane kernel's row epilogues only
-        if (d->mode != 1 || d->stride != 1 || d->dil != 1 || d->Hi != d->Ho || d->Wi != d->Wo || (unsigned)d->sub_y > 1u ||
-            (unsigned)d->sub_x > 1u || d->dtype != DML_F32)
-            return DML_EINVAL;
-        if ((int64_t)4 * d->B * d->Ho * d->Wo * (int64_t)d->ldy * 4 >= (1ll << 31)) return DML_EUNSUPPORTED;
-    }
+    cc::ConvChoice c;
+    const int rc = cc::conv_choose(d, conv_switches(), &c);
+    if (rc) return rc;
+    const ConvArgs a = conv_args(d, c);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((a.sub_grid || a.pad_x != a.pad) && (d->dtype == DML_BF16 || a.acc32)) return DML_EUNSUPPORTED;
-    if (a.acc32) return launch_conv<bf16_t, 2>(a, st);
-    if (d->dtype == DML_BF16)
-        return d->mode == 0 ? launch_conv<bf16_t, 0>(a, st) : launch_conv<bf16_t, 1>(a, st);
-    // fp32: only the two-plane kernel writes the BN-backward sums / adds the masked identity-branch gradient / maps a sub-grid
-    if ((a.bnr_partials || a.res_dz || a.sub_grid || a.pad_x != a.pad) && !conv_ws_planes_eligible(a, d->mode)) return DML_EUNSUPPORTED;
-    // x == x_planes: the caller keeps this operand as fp16 planes ONLY (no fp32 tensor behind `x`).  Every other fp32 kernel would
-    // read the planes as floats: refuse instead of falling back
-    if (d->f32_split == 2 && d->x_planes && d->x == d->x_planes && !conv_ws_planes_eligible(a, d->mode)) return DML_EUNSUPPORTED;
-    return d->mode == 0 ? launch_conv<float, 0>(a, st) : launch_conv<float, 1>(a, st);
-}
-
-extern "C" int dml_conv_wgrad(const DmlWgradDesc* d, void* stream) {
-    if (!d || !d->x || !d->dy || !d->dw) return DML_EINVAL;
-    if (d->dtype != DML_F32 && d->dtype != DML_BF16) return DML_EINVAL;
-    const int vec = d->dtype == DML_BF16 ? 8 : 4;
-    if (d->C % vec || d->ldx % vec || d->N % vec || d->ldy % vec) return DML_EALIGN;
-    if ((int64_t)d->B * d->Ho * d->Wo >= (1ll << 31)) return DML_EINVAL;
-    WgradArgs a;
-    a.x = d->x; a.dy = d->dy; a.dw = d->dw;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C = d->C; a.ldx = d->ldx;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N; a.ldy = d->ldy;
-    a.R = d->R; a.S = d->S; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
-    a.M = d->B * d->Ho * d->Wo;
-    a.Ktot = d->R * d->S * d->C;
-    a.nblk_n = (a.N + 127) / 128;
-    a.nblk_k = (a.Ktot + 127) / 128;
-    a.div_wo = make_fastdiv((uint32_t)d->Wo);
-    a.div_howo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
-    a.div_c = make_fastdiv((uint32_t)d->C);
-    a.x_planes = nullptr; a.dy_planes = nullptr; a.x_unscale = nullptr; a.dy_unscale = nullptr; a.x_plane_bytes = a.dy_plane_bytes = 0;
-    bool planes = false;
-    if (d->dtype == DML_F32 && d->f32_split == 2 && d->x_planes && d->dy_planes) {
-        if (!d->x_unscale || !d->dy_unscale || d->x_plane_stride <= 0 || d->dy_plane_stride <= 0) return DML_EINVAL;
-        if ((reinterpret_cast<uintptr_t>(d->x_planes) & 15) || (reinterpret_cast<uintptr_t>(d->dy_planes) & 15) ||
-            (d->x_plane_stride & 7) || (d->dy_plane_stride & 7))
-            return DML_EALIGN;
-        const int64_t xpb = (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2, ypb = (((int64_t)a.M - 1) * a.ldy + a.N) * 2;
-        // fp16 vectors of 8: C, N, pitches multiples of 8; both planes within 31-bit offsets
-        planes = d->C % 8 == 0 && d->N % 8 == 0 && d->ldx % 8 == 0 && d->ldy % 8 == 0 && xpb + d->x_plane_stride * 2 < 0x7fffffffll &&
-                 ypb + d->dy_plane_stride * 2 < 0x7fffffffll;
-        if (planes) {
-            a.x_planes = d->x_planes; a.dy_planes = d->dy_planes; a.x_unscale = d->x_unscale; a.dy_unscale = d->dy_unscale;
-            a.x_plane_bytes = (uint32_t)(d->x_plane_stride * 2); a.dy_plane_bytes = (uint32_t)(d->dy_plane_stride * 2);
-        }
-    }
-    // x == x_planes / dy == dy_planes: that operand exists as fp16 planes ONLY -- the fp32 kernels below must not read it as floats
-    if (!planes && ((d->x_planes && d->x == d->x_planes) || (d->dy_planes && d->dy == d->dy_planes))) return DML_EUNSUPPORTED;
-    const int tiles = (a.M + BK - 1) / BK;
-    const int cm = d->Cm > 0 ? d->Cm : d->C;
-    if (cm > d->C) return DML_EINVAL;
-    if (cm != d->C && !d->ws) return DML_EINVAL;      // dropping padded channels needs the workspace path
-    const int64_t plane = (int64_t)a.N * a.Ktot;
-    // With a workspace every weight gradient is a fixed-order sum of slabs: the train step is bitwise reproducible.  (Small
-    // weight tensors -- below 64 K elements -- used to take fp32 atomics instead, the reduce pass being latency-bound there;
-    // DML_WGRAD_ATOMICS=1 restores that.)  Without a workspace: atomics.
-    const bool use_ws = d->ws != nullptr;
-    int splitk = d->splitk;
-    if (splitk <= 0) {
-        const int base = a.nblk_n * a.nblk_k;
-        if (use_ws) {
-            // measured (tools/bench_conv.py): >= 512 workgroups and ~48 K tiles per workgroup
-            splitk = (512 + base - 1) / base;
-            if (tiles / 48 > splitk) splitk = tiles / 48;
-        } else {
-            splitk = (1024 + base - 1) / base;
-        }
-        const int cap = (tiles + 7) / 8;
-        if (splitk > cap) splitk = cap;
-        if (splitk < 1) splitk = 1;
-    }
-    if (use_ws && (int64_t)splitk * plane > d->ws_elems) splitk = (int)(d->ws_elems / plane);
-    if (use_ws && splitk < 1) return DML_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // large-tile kernel: bf16, whole 256-channel output tiles, everything addressable with 31-bit byte offsets and
-    // 24-bit pixel indices.  Measured (tools/bench_conv.py wgrad, incl. the reduce pass, vs the 128 x 128 kernel):
-    // decoder 3x3 320->256 @192^2 970 vs 727 TFLOP/s, 3x3 512->512 d2 879 vs 669, ASPP 3x3 2048->256 857 vs 693,
-    // layer3 3x3 256->256 569 vs 500.  With 4 output tiles (the 1x1 256<->1024 layers) filling 256 CUs would take 64
-    // splits and the slab traffic eats the gain, so those run as 128 workgroups (32 splits): standalone that is a
-    // few % slower than the small-tile kernel, but the weight gradients share the chip with the main stream and what
-    // counts there is CU-time -- whole step +0.75 % (3 interleaved A/B runs of bench.py).
-    const int64_t xb64 = (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2;
-    const int64_t yb64 = (((int64_t)a.M - 1) * a.ldy + a.N) * 2;
-    if (d->dtype == DML_BF16 && use_ws && a.N % 256 == 0 && (a.N / 256) * ((a.Ktot + 255) / 256) >= 4 &&
-        tiles >= 16 &&
-        xb64 < (1ll << 31) && yb64 < (1ll << 31) && (int64_t)(a.B + 1) * a.Hi * a.Wi < (1 << 24) && a.M < (1 << 24) &&
-        a.ldx < (1 << 22) && a.ldy < (1 << 22)) {
-        a.nblk_n = a.N / 256;
-        a.nblk_k = (a.Ktot + 255) / 256;
-        const int base = a.nblk_n * a.nblk_k;
-        int sk = d->splitk;
-        if (sk <= 0) {
-            // one workgroup per CU: pick the split count that fills whole rounds of 256 (128) workgroups best,
-            // fewest splits on ties (less slab traffic); at least 8 K steps per workgroup
-            int smax = tiles / 8;
-            if (smax > 256) smax = 256;
-            if ((int64_t)smax * plane > d->ws_elems) smax = (int)(d->ws_elems / plane);
-            if (smax < 1) smax = 1;
-            double best = -1.0;
-            sk = 1;
-            for (int c = 1; c <= smax; ++c) {
-                const int slab = (tiles + c - 1) / c;
-                const int real = (tiles + slab - 1) / slab;
-                const int blocks = base * real;
-                const int rnd = base < 6 ? 128 : 256;
-                const double eff = (double)blocks / (double)(((blocks + rnd - 1) / rnd) * rnd);
-                if (eff > best + 1e-9) { best = eff; sk = real; }
-            }
-        }
-        if ((int64_t)sk * plane > d->ws_elems) sk = (int)(d->ws_elems / plane);
-        if (sk < 1) return DML_EINVAL;
-        if (sk > tiles) sk = tiles;
-        a.ws = d->ws;
-        a.slab_tiles = (tiles + sk - 1) / sk;
-        sk = (tiles + a.slab_tiles - 1) / a.slab_tiles;
-        hipLaunchKernelGGL(conv_wgrad_big_kernel<WGRAD_DEPTH>, dim3(base * sk), dim3(WB_THREADS), 0, st, a, (uint32_t)xb64, (uint32_t)yb64);
-        const int64_t nrs = (int64_t)a.N * a.R * a.S;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(nrs * cm, 256), 1), dim3(256), 0, st, d->ws, d->dw, sk, nrs,
-                           cm, d->C, 1, 0);
-        DML_LAUNCH_CHECK();
-        return 0;
-    }
-    if (planes && use_ws && a.N % WGW_TN == 0 && tiles >= 16 && (reinterpret_cast<uintptr_t>(d->ws) & 15) == 0) {
-        // wave-specialised kernel on planes: 128 x 256 output tiles, persistent workgroups over (tile, slab) items.  Against
-        // conv_wgrad_h2_kernel in isolation (same box, tools/bench_h2.py wgrad): 3x3 256 -> 256 167-176 -> 149 us, 1x1 1024 <-> 256
-        // 76-83 -> 69-71, ASPP 3x3 1070-1147 -> 939, 3x3 512 -> 512 563 -> 473, decoder 3x3 2614-2724 -> 2532; in the train step,
-        // where the weight gradients share the chip with the main stream, the step is unchanged (183.6 vs 183.2 images/s, three
-        // interleaved pairs): DESIGN.md section 5, round 4
-        a.nblk_n = a.N / WGW_TN;
-        a.nblk_k = (a.Ktot + WGW_TK - 1) / WGW_TK;
-        const int base = a.nblk_n * a.nblk_k;
-        int sk = d->splitk;
-        if (sk <= 0) {
-            // the split count with the smallest modelled time: rounds of 256 workgroups x (K steps of an item x 1.45 us + 8 us for
-            // its 128 KB slab store and the restart of the K loop) + the fold pass over the slabs (written and read once, ~4 TB/s);
-            // >= 16 K steps per item.  (Round 4 maximised the filling of the rounds alone and took 71 slabs of 16 steps for 3x3
-            // 256 -> 256 -- five rounds, a third of each an epilogue, 335 MB of slabs -- where 14 slabs of 83 steps fill one round.)
-            int smax = tiles / 16;
-            if (smax > 256) smax = 256;
-            if ((int64_t)smax * plane > d->ws_elems) smax = (int)(d->ws_elems / plane);
-            if (smax < 1) smax = 1;
-            double best = 1e30;
-            sk = 1;
-            for (int c = 1; c <= smax; ++c) {
-                const int slab = (tiles + c - 1) / c;
-                const int real = (tiles + slab - 1) / slab;
-                const int items = base * real;
-                const double t = (double)((items + 255) / 256) * (slab * 1.45 + 8.0) + (double)real * (double)plane * 8.0 / 4.0e6;
-                if (t < best - 1e-9) { best = t; sk = real; }
-            }
-        }
-        if ((int64_t)sk * plane > d->ws_elems) sk = (int)(d->ws_elems / plane);
-        if (sk < 1) return DML_EINVAL;
-        if (sk > tiles) sk = tiles;
-        a.ws = d->ws;
-        a.slab_tiles = (tiles + sk - 1) / sk;
-        sk = (tiles + a.slab_tiles - 1) / a.slab_tiles;
-        const int nitems = base * sk;
-        const uint32_t xpb = (uint32_t)((((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2), ypb = (uint32_t)((((int64_t)a.M - 1) * a.ldy + a.N) * 2);
-        // (one item per workgroup instead of persistent workgroups, with and without a high-priority main stream: no change of the
-        // overlapped step, 83.4-83.9 ms in every combination, serial 86.1 -- profiles/r05_ab_wgrad_nonpersist_priority.txt)
-        const dim3 wgrid(nitems < 256 ? nitems : 256), wblock((4 + WGW_NLD) * 64);
-        if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0)
-            hipLaunchKernelGGL(conv_wgrad_ws_kernel<true>, wgrid, wblock, 0, st, a, xpb, ypb, nitems);
-        else
-            hipLaunchKernelGGL(conv_wgrad_ws_kernel<false>, wgrid, wblock, 0, st, a, xpb, ypb, nitems);
-        const int64_t nrs = (int64_t)a.N * a.R * a.S;
-        // (one-wave blocks: they start beside the persistent data-gradient workgroups of the other stream instead of waiting for one
-        // to retire -- 28.6 us per launch in the overlapped trace against 9.8 alone, 122 launches per step; see dml_bn_bwd_apply)
-        constexpr int rt = 64;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(nrs * cm, rt, 256 * 8 * (256 / rt)), 1), dim3(rt), 0, st, d->ws, d->dw, sk, nrs,
-                           cm, d->C, 1, 0);
-        DML_LAUNCH_CHECK();
-        return 0;
-    }
-    a.ws = use_ws ? d->ws : nullptr;
-    // N <= 64 (bf16): 64 x 256 tiles instead of half-empty 128 x 128 ones
-    // (measured, tools/bench_conv.py wgrad at 192 x 192: 3x3 64 -> 64 164 -> 160 us; the 1x1 layers are bound by the
-    // operand loads, not by the idle MFMA rows, and LOSE 20 % with the wider x tile -- they stay on the 128 x 128 kernel)
-    const bool n64 = d->dtype == DML_BF16 && a.N <= 64 && a.R * a.S > 1;
-    if (n64) {
-        a.nblk_n = 1;
-        a.nblk_k = (a.Ktot + 255) / 256;
-        if (d->splitk <= 0) {
-            const int base = a.nblk_k;
-            splitk = use_ws ? (512 + base - 1) / base : (1024 + base - 1) / base;
-            if (use_ws && tiles / 48 > splitk) splitk = tiles / 48;
-            const int cap = (tiles + 7) / 8;
-            if (splitk > cap) splitk = cap;
-            if (splitk < 1) splitk = 1;
-            if (use_ws && (int64_t)splitk * plane > d->ws_elems) splitk = (int)(d->ws_elems / plane);
-        }
-    }
-    if (splitk > tiles) splitk = tiles > 0 ? tiles : 1;
-    a.slab_tiles = (tiles + splitk - 1) / splitk;
-    splitk = (tiles + a.slab_tiles - 1) / a.slab_tiles;
-    dim3 grid(a.nblk_n * a.nblk_k * splitk);
-    // split-product kernel: operands through buffer descriptors (32-bit byte offsets)
-    const int64_t x3_xb = (((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 4, x3_yb = (((int64_t)a.M - 1) * a.ldy + a.N) * 4;
-    const bool x3_ok = x3_xb < (int64_t)0x7fffffff && x3_yb < (int64_t)0x7fffffff;
-    if (planes) {
-        const uint32_t xpb = (uint32_t)((((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2), ypb = (uint32_t)((((int64_t)a.M - 1) * a.ldy + a.N) * 2);
-        if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0)
-            hipLaunchKernelGGL(conv_wgrad_h2_kernel<true>, grid, dim3(NTHREADS), 0, st, a, xpb, ypb);
-        else
-            hipLaunchKernelGGL(conv_wgrad_h2_kernel<false>, grid, dim3(NTHREADS), 0, st, a, xpb, ypb);
-    } else if (n64)
-        hipLaunchKernelGGL(conv_wgrad_n64_kernel, grid, dim3(NTHREADS), 0, st, a);
-    else if (d->dtype == DML_BF16)
-        hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(NTHREADS), 0, st, a);
-    else if (d->f32_split && x3_ok) {
-        if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0)
-            hipLaunchKernelGGL(conv_wgrad_x3_kernel<true>, grid, dim3(NTHREADS), 0, st, a, (uint32_t)x3_xb, (uint32_t)x3_yb);
-        else
-            hipLaunchKernelGGL(conv_wgrad_x3_kernel<false>, grid, dim3(NTHREADS), 0, st, a, (uint32_t)x3_xb, (uint32_t)x3_yb);
-    } else
-        hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(NTHREADS), 0, st, a);
-    if (use_ws) {
-        const int64_t nrs = (int64_t)a.N * a.R * a.S;
-        // small tensors with very many splits: fold chunks of 16 splits first (two launches, see wgrad_reduce_kernel)
-        const int ychunks = (nrs * cm < 65536 && splitk > 64) ? (splitk + 15) / 16 : 1;
-        if (ychunks > 1) {
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(nrs * cm, 256), ychunks), dim3(256), 0, st, d->ws, d->dw, splitk,
-                               nrs, cm, d->C, 1, 1);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(nrs * cm, 256)), dim3(256), 0, st, d->ws, d->dw, ychunks, nrs, cm,
-                               d->C, 16, 0);
-        } else {
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(nrs * cm, 256)), dim3(256), 0, st, d->ws, d->dw, splitk, nrs, cm,
-                               d->C, 1, 0);
-        }
+    if (c.elem_bytes == 2) {
+        if (c.mode == 2) launch_conv<bf16_t, 2>(c, a, st);
+        else if (c.mode == 1) launch_conv<bf16_t, 1>(c, a, st);
+        else launch_conv<bf16_t, 0>(c, a, st);
+    } else {
+        if (c.mode == 1) launch_conv<float, 1>(c, a, st);
+        else launch_conv<float, 0>(c, a, st);
     }
     DML_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int dml_conv_wgrad_group_eligible(const DmlWgradDesc* d) { return wgrad_big_eligible(d) ? 1 : 0; }
+extern "C" int dml_conv_wgrad(const DmlWgradDesc* d, void* stream) {
+    cc::WgradChoice c;
+    const int rc = cc::wgrad_choose(d, &c);
+    if (rc) return rc;
+    WgradArgs a;
+    fill_wgrad_args(a, d, c.planes);
+    a.nblk_n = c.nblk_n; a.nblk_k = c.nblk_k; a.slab_tiles = c.slab_tiles;
+    a.ws = c.use_ws ? d->ws : nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(c.grid), block(c.block);
+    switch (c.family) {
+    case cc::WGRAD_BIG:
+        hipLaunchKernelGGL(conv_wgrad_big_kernel<WGRAD_DEPTH>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes);
+        break;
+    case cc::WGRAD_WS:
+        if (c.lin) hipLaunchKernelGGL(conv_wgrad_ws_kernel<true>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes, c.nitems);
+        else hipLaunchKernelGGL(conv_wgrad_ws_kernel<false>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes, c.nitems);
+        break;
+    case cc::WGRAD_H2:
+        if (c.lin) hipLaunchKernelGGL(conv_wgrad_h2_kernel<true>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes);
+        else hipLaunchKernelGGL(conv_wgrad_h2_kernel<false>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes);
+        break;
+    case cc::WGRAD_N64:
+        hipLaunchKernelGGL(conv_wgrad_n64_kernel, grid, block, 0, st, a);
+        break;
+    case cc::WGRAD_X3:
+        if (c.lin) hipLaunchKernelGGL(conv_wgrad_x3_kernel<true>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes);
+        else hipLaunchKernelGGL(conv_wgrad_x3_kernel<false>, grid, block, 0, st, a, c.x_bytes, c.dy_bytes);
+        break;
+    default:
+        if (c.elem_bytes == 2) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, block, 0, st, a);
+        break;
+    }
+    for (int i = 0; i < c.nreduce; ++i) {
+        const cc::ReduceLaunch& r = c.reduce[i];
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(r.grid_x, r.grid_y), dim3(r.block), 0, st, d->ws, d->dw, r.splits, c.nrs, c.cm, d->C,
+                           r.slab_stride, r.fold_only);
+    }
+    DML_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dml_conv_wgrad_group_eligible(const DmlWgradDesc* d) { return cc::wgrad_big_eligible(d, true) ? 1 : 0; }
 
 // Weight gradients of several layers in one launch (conv_wgrad_group_kernel) + one fold launch.  Every job must pass
 // dml_conv_wgrad_group_eligible; the descriptors' own ws / ws_elems / splitk fields are ignored: the shared workspace
-// `ws` is partitioned here.  Splits are chosen so that the launch is one round of <= 256 workgroups with about the
-// same number of pixel tiles per workgroup in every job.
+// `ws` is partitioned by wgrad_group_choose.
 extern "C" int dml_conv_wgrad_group(const DmlWgradDesc* const* descs, int n, float* ws, int64_t ws_elems, void* stream) {
-    if (!descs || n <= 0 || n > WG_MAX_JOBS || !ws) return DML_EINVAL;
+    cc::WgradGroupChoice c;
+    const int rc = cc::wgrad_group_choose(descs, n, ws, ws_elems, &c);
+    if (rc) return rc;
     WgradGroup g;
     ReduceGroup r;
-    int base[WG_MAX_JOBS], tiles[WG_MAX_JOBS], sk[WG_MAX_JOBS];
-    int64_t plane[WG_MAX_JOBS];
-    double work = 0.0;
-    int tbase = 0;
-    for (int j = 0; j < n; ++j) {
-        const DmlWgradDesc* d = descs[j];
-        if (!wgrad_big_eligible(d)) return DML_EUNSUPPORTED;
-        WgradArgs& a = g.job[j];
-        fill_wgrad_args(a, d);
-        a.nblk_n = a.N / 256;
-        a.nblk_k = (a.Ktot + 255) / 256;
-        base[j] = a.nblk_n * a.nblk_k;
-        tiles[j] = (a.M + BK - 1) / BK;
-        plane[j] = (int64_t)a.N * a.Ktot;
-        work += (double)base[j] * tiles[j];
-        tbase += base[j];
-        g.xb[j] = (uint32_t)((((int64_t)(a.B * a.Hi) * a.Wi - 1) * a.ldx + a.C) * 2);
-        g.yb[j] = (uint32_t)((((int64_t)a.M - 1) * a.ldy + a.N) * 2);
-    }
-    const int budget = tbase <= 256 ? 256 : ((tbase + 255) / 256) * 256;
-    int blocks = 0;
-    for (int j = 0; j < n; ++j) {
-        int s = (int)((double)tiles[j] * budget / work);             // equal pixel tiles per workgroup
-        const int cap = tiles[j] / 8 > 0 ? tiles[j] / 8 : 1;          // at least 8 K steps per workgroup
-        if (s > cap) s = cap;
-        if (s < 1) s = 1;
-        sk[j] = s;
-        blocks += base[j] * s;
-    }
-    // hand the remaining workgroups of the round to the jobs whose workgroups are the longest
-    for (;;) {
-        int best = -1;
-        double longest = 0.0;
-        for (int j = 0; j < n; ++j) {
-            const double per = (double)tiles[j] / sk[j];
-            if (blocks + base[j] <= budget && sk[j] < tiles[j] / 8 && per > longest) { longest = per; best = j; }
-        }
-        if (best < 0) break;
-        ++sk[best];
-        blocks += base[best];
-    }
-    int64_t off = 0;
     g.njobs = r.njobs = n;
     g.start[0] = 0;
-    int64_t max_items = 0;
     for (int j = 0; j < n; ++j) {
-        WgradArgs& a = g.job[j];
-        a.slab_tiles = (tiles[j] + sk[j] - 1) / sk[j];
-        sk[j] = (tiles[j] + a.slab_tiles - 1) / a.slab_tiles;
-        if (off + (int64_t)sk[j] * plane[j] > ws_elems) return DML_EINVAL;      // workspace too small for this group
-        a.ws = ws + off;
-        g.start[j + 1] = g.start[j] + base[j] * sk[j];
         const DmlWgradDesc* d = descs[j];
-        const int cm = d->Cm > 0 ? d->Cm : d->C;
-        r.ws[j] = a.ws; r.dw[j] = d->dw; r.splits[j] = sk[j]; r.Cm[j] = cm; r.Cp[j] = d->C;
-        r.NRS[j] = (int64_t)a.N * a.R * a.S;
-        if (r.NRS[j] * cm > max_items) max_items = r.NRS[j] * cm;
-        off += (int64_t)sk[j] * plane[j];
+        WgradArgs& a = g.job[j];
+        fill_wgrad_args(a, d, false);
+        a.nblk_n = c.nblk_n[j]; a.nblk_k = c.nblk_k[j]; a.slab_tiles = c.slab_tiles[j];
+        a.ws = ws + c.ws_off[j];
+        g.xb[j] = c.x_bytes[j]; g.yb[j] = c.dy_bytes[j];
+        g.start[j + 1] = c.start[j + 1];
+        r.ws[j] = a.ws; r.dw[j] = d->dw; r.splits[j] = c.splitk[j]; r.Cm[j] = c.cm[j]; r.Cp[j] = d->C;
+        r.NRS[j] = c.nrs[j];
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(conv_wgrad_group_kernel<WGRAD_DEPTH>, dim3(g.start[n]), dim3(WB_THREADS), 0, st, g);
-    hipLaunchKernelGGL(wgrad_reduce_group_kernel, dim3(grid_for(max_items, 256, 1024), n), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(conv_wgrad_group_kernel<WGRAD_DEPTH>, dim3(c.grid), dim3(c.block), 0, st, g);
+    hipLaunchKernelGGL(wgrad_reduce_group_kernel, dim3(c.rgrid_x, c.rgrid_y), dim3(c.rblock), 0, st, r);
     DML_LAUNCH_CHECK();
     return 0;
 }

@@ -7,6 +7,19 @@ Imports ``/root/reference`` with the shims of SURVEY.md Appendix B (fake torchvi
 reference travels: fixtures hold inputs/seeds and expected outputs only.
 
     python tests/tools/mint_golden.py            # regenerate everything (~2 min on 8 cores)
+
+Not made here: ``tests/golden/conv_choice_cases.json.gz`` (tests/test_conv_choice.py; JSON, gzip-compressed with mtime 0: the
+text is 2.9 MB).  Its descriptors are (a) every distinct
+ConvDesc / WgradDesc in ``plan.keep`` and every ``dml_conv_wgrad_group`` op's ``args.meta`` of the train plans at 16x768x768 (bf16,
+f16x2, f32x3, exact fp32) and at the suite's small sizes, of the forward-only 8x768x768 and the inference 1x1024x2048 plans, dumped on
+a GPU box with pointers reduced to null / low four bits / "x is x_planes", and (b) hand-written cases around every threshold of the
+rules plus one per error return.  Its ``expect`` lines were minted once from the last commit whose ``conv_igemm.hip`` still chose and
+launched in one pass (ea42b4f): that file compiled ``--cuda-host-only`` with ``hipLaunchKernelGGL`` redefined to record the kernel
+expression with its template values, grid, block, the first argument (ConvArgs / WgradArgs / WgradGroup / ReduceGroup) and the integer
+arguments, ``DML_LAUNCH_CHECK`` empty, and a ``main`` that calls dml_conv_stat_rows / dml_conv_igemm / dml_conv_wgrad /
+dml_conv_wgrad_group on each descriptor under each switch setting (DML_CONV_V1, DML_CONV_BM256, DML_CONV_WS) and prints the line
+format of tests/tools/conv_choice_dump.cpp.  The expectations therefore never come from csrc/conv_choice.h; a rule change on purpose
+means re-minting the affected lines from the library that carries the new rule.
 """
 from __future__ import annotations
 
