@@ -610,6 +610,39 @@ int dml_loss_bwd(const float* logits, const int64_t* labels, const double* sums,
                  float n_images, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Focal loss (utils/loss.py:7-23 of the reference) of logits[B,K,H,W] fp32 (NCHW, contiguous) and labels[B,H,W] int64.
+ * A pixel is valid when its label != ignore_index; a valid label lies in [0, K) (the caller's duty, as for dml_loss_fwd).
+ * On a valid pixel
+ *   ce = logsumexp_k L_k - L_y      pt = exp(-ce)      u = 1 - pt      fl = alpha u^gamma ce
+ *   m  = alpha (u^gamma + gamma pt ce u^(gamma-1))     d fl / d L_k = m (softmax_k - [k = y])
+ * and fl = 0, gradient 0 on an ignored one.  Where u = 0 (pt rounds to 1): fl = 0, m = alpha for gamma = 0 and m = 0 for
+ * gamma > 0 -- the analytic limit; the reference's autograd gives NaN there for 0 < gamma < 1.  u^0 = 1 for every u.
+ * u is taken as -expm1(-ce), and the log-sum-exp keeps its largest term out of the sum (ce = max - L_y + log1p(rest)).
+ * size_average != 0: loss = sum fl / (B H W) -- the divisor counts the ignored pixels too (the reference's .mean() of a
+ * reduction='none' map) -- else loss = sum fl.  A batch with nothing valid has loss 0 and a zero gradient.
+ * DML_EINVAL (all three; nothing is launched): a NULL pointer other than gout, B, H or W <= 0, K < 1, gamma < 0, alpha or
+ * gamma not finite.
+ * 16-byte loads and stores (4 pixels per lane) when H W % 4 == 0 and logits, labels (and glogits) are 16-byte aligned, one
+ * float per lane otherwise; a pixel sees the same operations in the same order on either path (bitwise equal results).
+ * 64-bit offsets, grid-stride loops, any K >= 1.  No atomics: bitwise reproducible.
+ *
+ * dml_focal_loss_fwd: one pass over the logits.  sums (device, double[4]) = { sum fl over valid px, #valid px,
+ * #pixels = B H W, #correct (argmax == label) }: fp32 per lane, per-wave and per-workgroup partials in block_partials
+ * (3 x 2048 floats, device), then one workgroup folds them in double in a fixed order.
+ * ---------------------------------------------------------------------------------------------- */
+int dml_focal_loss_fwd(const float* logits, const int64_t* labels, double* sums, float* block_partials,
+                       int B, int K, int H, int W, int64_t ignore_index, float alpha, float gamma, void* stream);
+/* *loss (device float) = size_average ? sums[0] / sums[2] : sums[0].  A data-parallel caller all-reduces the four doubles
+ * first: the global pixel count travels in sums[2]. */
+int dml_focal_loss_finalize(const double* sums, float* loss, int size_average, void* stream);
+/* glogits[B,K,H,W] = gout * d loss / d logits; gout is a device scalar, NULL = 1.  The divisor is read from sums[2] on the
+ * device.  K <= 16: a pixel's logits stay in registers between the log-sum-exp and the gradient (read from memory once);
+ * more classes are read a second time. */
+int dml_focal_loss_bwd(const float* logits, const int64_t* labels, const double* sums, const float* gout,
+                       float* glogits, int B, int K, int H, int W, int64_t ignore_index, float alpha, float gamma,
+                       int size_average, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SGD with momentum and weight decay, torch semantics (main_embedding.py:385-388):
  *   g = gscale*g + wd*p ; v = mu*v + g ; p -= lr*v
  * ---------------------------------------------------------------------------------------------- */

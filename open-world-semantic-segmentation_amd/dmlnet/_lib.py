@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("DML_LIB_PATH") or os.path.join(_HERE, "libdmlnet_hip.
 DML_F32, DML_BF16 = 0, 1
 STAT_ROWS = 64
 LOSS_BLOCKS = 2048
+FOCAL_PARTIALS = 3 * 2048     # floats of dml_focal_loss_fwd's block_partials
 
 c_p = C.c_void_p
 c_i = C.c_int
@@ -196,6 +197,9 @@ _PROTOS = {
     "dml_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_p]),
     "dml_loss_finalize": (c_i, [c_p, c_p, c_f, c_f, c_p]),
     "dml_loss_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_p]),
+    "dml_focal_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_p]),
+    "dml_focal_loss_finalize": (c_i, [c_p, c_p, c_i, c_p]),
+    "dml_focal_loss_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_i, c_p]),
     "dml_sgd_step": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_p]),
     "dml_fill_f32": (c_i, [c_p, c_i64, c_f, c_p]),
     "dml_convert_dtype": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),

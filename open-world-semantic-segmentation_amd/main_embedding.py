@@ -34,6 +34,8 @@ def get_argparser():
     p.add_argument("--crop_size", type=int, default=768)
     p.add_argument("--loss_type", default="cross_entropy", choices=["cross_entropy", "dml", "focal_loss"])
     p.add_argument("--alpha", type=float, default=0.01, help="weight of the variance loss for --loss_type dml")
+    p.add_argument("--focal_alpha", type=float, default=1.0, help="alpha of --loss_type focal_loss")
+    p.add_argument("--focal_gamma", type=float, default=0.0, help="gamma of --loss_type focal_loss (>= 0)")
     p.add_argument("--ckpt", default=None)
     p.add_argument("--continue_training", action="store_true")
     p.add_argument("--save_dir", default="checkpoints")
@@ -95,16 +97,16 @@ def main():
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=opts.step_size, gamma=0.1)
     sync = True if world > 1 else None
     if opts.loss_type == "focal_loss":
-        # accepted by the reference's parser (main_embedding.py:72,398-399) but dead there: its train loop calls
-        # criterion(outputs, labels, features) (:467) and utils/loss.py:7-23 FocalLoss.forward takes two arguments -> TypeError
-        raise SystemExit("--loss_type focal_loss: the reference's FocalLoss (utils/loss.py:7-23) cannot run under its own "
-                         "embedding train loop (main_embedding.py:467 passes three arguments); use cross_entropy or dml")
-    if opts.loss_type == "dml":
+        # the reference's construction (main_embedding.py:398-399); its own FocalLoss.forward takes two arguments and fails under
+        # the train loop's criterion(outputs, labels, features) (:467), so utils.FocalLoss accepts the third and ignores it
+        criterion = utils.FocalLoss(ignore_index=255, size_average=True, alpha=opts.focal_alpha, gamma=opts.focal_gamma,
+                                    sync=sync)
+    elif opts.loss_type == "dml":
         criterion = utils.DMLLoss(alpha=opts.alpha, ignore_index=255, sync=sync, fused_backward=True)
     else:
         criterion = utils.CrossEntropyLoss(ignore_index=255, alpha=0, beta=0, gamma=0, sync=sync,
                                            fused_backward=True)                                   # :401
-    # fused_backward: the loss below is the only consumer of `outputs` (:466-470), so d(loss)/d(logits) is never
+    # fused_backward (cross_entropy, dml): the loss below is the only consumer of `outputs` (:466-470), so d(loss)/d(logits) is never
     # materialised -- the head's backward computes it on the fly (dmlnet/lazy_grad.py)
 
     cur_itrs, best_score = 0, 0.0
