@@ -51,57 +51,6 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ dy,
-                                                          const uint8_t* __restrict__ argmax, T* __restrict__ dx,
-                                                          int B, int H, int W, int C, int Ho, int Wo) {
-    constexpr int V = Vec16<T>::N;
-    const int CV = C / V;
-    const int64_t total = (int64_t)B * H * W * CV;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int cv = (int)(i % CV);
-        int64_t p = i / CV;
-        const int xi = (int)(p % W); p /= W;
-        const int yi = (int)(p % H);
-        const int b = (int)(p / H);
-        float acc[V];
-#pragma unroll
-        for (int q = 0; q < V; ++q) acc[q] = 0.f;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int ty = yi + 1 - r;
-            if (ty < 0 || (ty & 1)) continue;
-            const int yo = ty >> 1;
-            if (yo >= Ho) continue;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const int tx = xi + 1 - s;
-                if (tx < 0 || (tx & 1)) continue;
-                const int xo = tx >> 1;
-                if (xo >= Wo) continue;
-                const int64_t o = (((int64_t)b * Ho + yo) * Wo + xo) * C + cv * V;
-                float g[V];
-                Vec16<T>::load(dy + o, g);
-                uint8_t am[V];
-                if (V == 8) {
-                    const uint2 t = *reinterpret_cast<const uint2*>(argmax + o);
-                    const uint32_t w[2] = {t.x, t.y};
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) am[q] = (uint8_t)(w[q >> 2] >> ((q & 3) * 8));
-                } else {
-                    const uint32_t t = *reinterpret_cast<const uint32_t*>(argmax + o);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) am[q] = (uint8_t)(t >> (q * 8));
-                }
-#pragma unroll
-                for (int q = 0; q < V; ++q) acc[q] += (am[q] == r * 3 + s) ? g[q] : 0.f;
-            }
-        }
-        Vec16<T>::store(dx + (((int64_t)b * H + yi) * W + xi) * C + cv * V, acc);
-    }
-}
-
 // ------------------------------------------------------------------- reductions over HW / broadcasts
 // out[b][c] = scale * sum_{p < HW} x[b][p][c];  block = 8 vector columns (128 B of a row) x 32 row lanes, four rows in
 // flight per lane: with 32 x 8 the launch had B * C / 256 workgroups (16 for the 256-channel gradient of the pooled
@@ -465,7 +414,7 @@ extern "C" int dml_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* argmax, int
 
 extern "C" int dml_maxpool3x3s2_bwd(const void* dy, const uint8_t* argmax, void* dx, int B, int H, int W, int C,
                                     int dtype, void* stream) {
-    if (!dy || !argmax || !dx) return DML_EINVAL;
+    if (!dy || !argmax || !dx || B <= 0 || H <= 0 || W <= 0) return DML_EINVAL;
     if (!vec_ok(dtype, C)) return DML_EALIGN;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const int V = dtype == DML_BF16 ? 8 : 4;
