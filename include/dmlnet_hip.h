@@ -593,6 +593,41 @@ int dml_knn_cosine_score(const float* feats, float* score, int B, int C, int H, 
 int dml_dissum_msp_score(const float* logits, float* conf, float* work, int B, int K, int H, int W, int k_first,
                          float clip, float threshold, float slope, int prob_logit, void* stream);
 
+/* Dense CRF with one spatial Gaussian pairwise term on logits[B,K,H,W] fp32 (NCHW, contiguous) over the classes
+ * k_first <= k < K, C = K - k_first (k_first = 1: --exclude_back without a copy): anomaly/eval_ood_traditional.py:492-510 of
+ * the reference (`--ood crf-gauss`: pydensecrf's unary_from_softmax, addPairwiseGaussian(sxy = 3, compat = 3), inference(100),
+ * np.max over the classes).  Per image, y the row and x the column:
+ *   U_c = -log(min(max(softmax_c(L), clip), 1))
+ *   kx(d) = exp(-d^2 / (2 sx^2)) for |d| <= Rx = ceil(6 sx), else 0; ky, Ry alike with sy.  The tail cut at 6 sigma is 1.5e-8
+ *   of the centre tap.  Sums run over the pixels inside the image (nothing is padded) and include the pixel itself (d = 0).
+ *   nx(x) = 1 / sqrt(sum_x' kx(x - x')), ny(y) alike: densecrf's symmetric normalisation 1 / sqrt(sum_y',x' ky kx), factorised
+ *   M_c(y,x) = ny(y) nx(x) sum_y' ky(y - y') ny(y') sum_x' kx(x - x') nx(x') Q_c(y',x')
+ *   Q^0 = softmax_c(-U),  Q^{t+1} = softmax_c(-U + compat M(Q^t))              (PottsCompatibility(compat), inference(iters))
+ *   conf(y,x) = max_c Q^iters_c(y,x) (higher = in-distribution); map(y,x) = argmax_c, the lowest index on a tie, counted from
+ *   k_first.  map may be NULL.  iters = 0 gives the maximum of the re-normalised clipped softmax; compat = 0 gives the same
+ *   bits after any number of steps.
+ * work: dml_crf_gauss_workspace_bytes(B, C, H, W) = 4 (3 B C H W + H + W + 256) bytes -- U, Q and the row-filtered T, the two
+ * tap tables (128 floats each), nx[W], ny[H]; nothing beyond it is written.  A negative DML_E* code for a shape
+ * dml_crf_gauss rejects.
+ * 1 + 2 iters launches, ordered by the stream alone (no cooperative grid, flag or atomic): the init launch (U, Q^0, tables);
+ * per step a row launch (Q -> T through an LDS row tile with a halo of Rx) and a column launch (T with a halo of Ry through
+ * LDS, a pixel's C messages in registers, softmax fused; the last one writes conf and map instead of Q).  Traffic per step,
+ * in units of B C H W 4 bytes: Q read + T written + T read + U read + Q written = 5 (the column tile's halo rows, 2 Ry per
+ * 32 rows at C <= 16 and per 16 rows above, are re-read from cache).  16-byte accesses in the row launch when W % 4 == 0
+ * and work is 16-byte aligned, one float per lane otherwise and in the column launch.  Every sum has a fixed order: bitwise
+ * reproducible, image b of a batch equals the image alone.
+ * Two properties of the reference are deliberately not reproduced: (1) it calls DenseCRF2D(h, w, ch) although the
+ * constructor takes (width, height, nlabels), so on a non-square frame it filters over scrambled neighbourhoods -- here y is
+ * the row and x the column; (2) it takes ch from `scores`, not from `tmp_scores`, so with --exclude_back it stops at
+ * setUnaryEnergy -- here k_first = 1 works.  pydensecrf's permutohedral lattice approximates the Gaussian filter that is
+ * computed exactly here; the two do not agree digit for digit.
+ * DML_EINVAL: logits, conf or work NULL, B, K, H, W <= 0, k_first < 0 or >= K, iters < 0, sx, sy or clip not > 0, clip >= 1.
+ * DML_EUNSUPPORTED: K - k_first > 32, sx or sy > 8 (Rx, Ry <= 48), B > 65535 or B H W > 2^40.  Nothing is launched when a code
+ * is returned. */
+int64_t dml_crf_gauss_workspace_bytes(int B, int C, int H, int W);
+int dml_crf_gauss(const float* logits, float* conf, int64_t* map, void* work, int B, int K, int H, int W, int k_first,
+                  float sx, float sy, float compat, int iters, float clip, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DML loss = CE(-dist^2)/n + alpha * VAR/n (anomaly/models/models.py:42-78; live part of
  * utils/loss.py:34-42 is alpha = 0).

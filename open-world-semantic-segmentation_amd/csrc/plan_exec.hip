@@ -102,6 +102,7 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_open_world_post),
     DML_ENTRY(dml_novel_relabel_multi),
     DML_ENTRY(dml_knn_cosine_score),
+    DML_ENTRY(dml_crf_gauss),
     DML_ENTRY(dml_loss_fwd),
     DML_ENTRY(dml_loss_finalize),
     DML_ENTRY(dml_loss_bwd),

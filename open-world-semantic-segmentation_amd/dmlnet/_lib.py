@@ -194,6 +194,8 @@ _PROTOS = {
                                   c_p]),
     "dml_novel_relabel_multi": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dml_knn_cosine_score": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "dml_crf_gauss_workspace_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
+    "dml_crf_gauss": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_p]),
     "dml_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_p]),
     "dml_loss_finalize": (c_i, [c_p, c_p, c_f, c_f, c_p]),
     "dml_loss_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_p]),

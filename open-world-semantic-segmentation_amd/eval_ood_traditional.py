@@ -12,7 +12,13 @@ and :511-530: knn -- the sum, over the 8 x 8 pixels down-right and the
 8 x 8 pixels up-left of each pixel, of the cosine similarity between its embedding `ft1` and theirs, 0 beyond the image
 border: the reference's 128 rounds of zero-filled shifted copies in one kernel, utils.knn_cosine_score; its plt.figure /
 imshow / show calls and its resize of the map to segSize, the identity on a map that already has that size, are not
-reproduced; the two CRF variants of the reference need pydensecrf and are not offered), then `eval_ood_measure`
+reproduced; and :492-510: crf-gauss -- a dense CRF on the scores whose only pairwise term is a spatial Gaussian
+(sxy = 3, Potts compat = 3, 100 mean-field steps), conf = the largest marginal: the reference copies the scores to the host
+and runs pydensecrf's lattice on one CPU thread, here each step is two 1-D blurs and a softmax on the device,
+utils.dense_crf_gauss, with the intended geometry (the reference passes (h, w) where DenseCRF2D takes (width, height)) and
+no copy for --exclude_back (the reference stops at setUnaryEnergy with it).  The other CRF variant, `crf`, is not offered:
+its bilateral kernel over the 13-channel scores needs a 15-dimensional lattice filter, which is not separable), then
+`eval_ood_measure`
 (:128-148) and the pixel accuracy / IoU meters (:548-556) -- all on the device; nothing but the three OOD numbers and
 the confusion counts per frame reaches the host.
 Data: a StreetHazards-layout tree from disk (the reference's command line: `--cfg FILE`, `--gpu`, `--ood`,
@@ -36,6 +42,9 @@ IMG_SIZES, IMG_MAX_SIZE, PADDING_CONSTANT = (300, 375, 450, 525, 600), 1000, 8
 # the gate of `--ood dissum_msp`: the reference's Coefficient_map(dis_sum, 0.2) with lamda = 50 (:104-106,447); main() puts
 # --mix_threshold / --mix_slope here
 MIX = {"threshold": 0.2, "slope": 50.0}
+# `--ood crf-gauss`: the reference's addPairwiseGaussian(sxy=3, compat=3) and inference(100) (:501,504); main() puts
+# --crf_sxy / --crf_compat / --crf_iters here
+CRF = {"sxy": 3.0, "compat": 3.0, "iters": 100}
 
 
 def resized_shapes(h, w):
@@ -46,9 +55,10 @@ def resized_shapes(h, w):
 
 
 def confidence(scores, ood, exclude_back=False, feats=None):
-    """:275-340, :434-448, :511-530.  scores [1, K, H, W] on the device -> conf [H, W] on the device.  `knn` reads the
+    """:275-340, :434-448, :492-530.  scores [1, K, H, W] on the device -> conf [H, W] on the device.  `knn` reads the
     embedding feats [1, C, H, W] instead of the scores (the reference's `ft1`), so --exclude_back does not touch it.
-    `dissum_msp` takes its gate from MIX and skips the background class inside the kernel."""
+    `dissum_msp` takes its gate from MIX, `crf-gauss` its kernel width, strength and step count from CRF; both skip the
+    background class inside the kernel."""
     if ood == "knn":
         if feats is None:
             raise ValueError("--ood knn scores the embedding: pass feats")
@@ -56,6 +66,9 @@ def confidence(scores, ood, exclude_back=False, feats=None):
     if ood == "dissum_msp":
         return utils.dissum_msp_score(scores, clip=400.0, threshold=MIX["threshold"], slope=MIX["slope"],
                                       first_class=1 if exclude_back else 0)[0]
+    if ood == "crf-gauss":
+        return utils.dense_crf_gauss(scores, sxy=CRF["sxy"], compat=CRF["compat"], iters=CRF["iters"],
+                                     first_class=1 if exclude_back else 0)[0]
     tmp = scores[:, 1:].contiguous() if exclude_back else scores
     if ood == "msp":
         return utils.argmax_msp(tmp)[1][0]
@@ -155,11 +168,17 @@ def load_cfg(cfg_file, overrides):
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--ood", default="dissum", choices=["msp", "maxlogit", "dissum", "background", "knn",
-                                                           "dissum_msp"])
+                                                           "dissum_msp", "crf-gauss"])
     p.add_argument("--mix_threshold", type=float, default=MIX["threshold"],
                    help="--ood dissum_msp: the normalised distance sum at which the gate is 1/2 (the reference's 0.2)")
     p.add_argument("--mix_slope", type=float, default=MIX["slope"],
                    help="--ood dissum_msp: the gate's steepness (the reference's lamda = 50)")
+    p.add_argument("--crf_sxy", type=float, default=CRF["sxy"],
+                   help="--ood crf-gauss: the Gaussian's standard deviation in pixels (the reference's sxy = 3; at most 8)")
+    p.add_argument("--crf_compat", type=float, default=CRF["compat"],
+                   help="--ood crf-gauss: the Potts strength of the pairwise term (the reference's compat = 3)")
+    p.add_argument("--crf_iters", type=int, default=CRF["iters"],
+                   help="--ood crf-gauss: mean-field steps (the reference's inference(100))")
     p.add_argument("--exclude_back", action="store_true")
     p.add_argument("--out_label", type=int, default=13, help="cfg.OOD.out_labels: the anomaly id of StreetHazards")
     p.add_argument("--num_images", type=int, default=4)
@@ -181,6 +200,7 @@ def build_parser():
 def main():
     opts = build_parser().parse_args()
     MIX.update(threshold=opts.mix_threshold, slope=opts.mix_slope)
+    CRF.update(sxy=opts.crf_sxy, compat=opts.crf_compat, iters=opts.crf_iters)
     device = torch.device("cuda", opts.gpu)
     torch.cuda.set_device(device)
     torch.manual_seed(304)

@@ -1,5 +1,5 @@
 """Open-world scores computed on the device instead of on 134 MB/img host copies
-(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305,434-448,511-530)."""
+(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305,434-448,492-510,511-530)."""
 from __future__ import annotations
 
 import numpy as np
@@ -85,6 +85,48 @@ def knn_cosine_score(feats: torch.Tensor, neighbor_size: int = 9) -> torch.Tenso
     _lib.check(lib.dml_knn_cosine_score(feats.data_ptr(), score.data_ptr(), B, C, H, W, int(neighbor_size), _st(feats)),
                "dml_knn_cosine_score")
     return score
+
+
+# dense_crf_gauss's workspace, one per device: {device index: ((B, C, H, W), uint8 tensor)}.  A frame of another shape replaces
+# it, so a driver that walks a dataset holds one workspace, not one per size.
+_CRF_WORK = {}
+
+
+def dense_crf_gauss(scores: torch.Tensor, sxy=3.0, compat: float = 3.0, iters: int = 100, first_class: int = 0,
+                    clip: float = 1e-5, return_map: bool = False):
+    """Dense-CRF confidence of scores [B, K, H, W] (fp32, CUDA) over the classes first_class .. K - 1 -> conf [B, H, W]
+    (dml_crf_gauss): the unary -log(clipped softmax) of pydensecrf's unary_from_softmax, one spatial Gaussian pairwise term
+    (sxy, a float or an (sx, sy) pair as addPairwiseGaussian takes it; Potts compat), `iters` mean-field steps and the
+    maximum over the classes -- anomaly/eval_ood_traditional.py:492-510 of the reference with its defaults sxy = 3,
+    compat = 3, inference(100).  The Gaussian filter is computed exactly, as two 1-D passes per step, where pydensecrf's
+    lattice approximates it; y is the row and x the column (the reference swaps them in DenseCRF2D(h, w, ch)), and
+    first_class=1 is --exclude_back without a copy (the reference stops there).  return_map=True also returns the int64
+    arg-max map [B, H, W], counted from first_class.  The workspace is kept per device and shape; calls that share it
+    must be ordered on one stream."""
+    _need_cuda(scores)
+    if scores.dim() != 4:
+        raise ValueError("scores must be [B, K, H, W]")
+    if scores.dtype != torch.float32:
+        raise TypeError("scores must be float32, not %s" % (scores.dtype,))
+    sx, sy = (sxy if isinstance(sxy, (tuple, list)) else (sxy, sxy))
+    lib = _lib.load()
+    scores = scores.contiguous()
+    B, K, H, W = scores.shape
+    C = K - int(first_class)
+    nbytes = lib.dml_crf_gauss_workspace_bytes(B, C, H, W)
+    _lib.check(min(nbytes, 0), "dml_crf_gauss_workspace_bytes")
+    key = (B, C, H, W)
+    held = _CRF_WORK.get(scores.device.index)
+    if held is None or held[0] != key:
+        _CRF_WORK.pop(scores.device.index, None)
+        held = (key, torch.empty(nbytes, dtype=torch.uint8, device=scores.device))
+        _CRF_WORK[scores.device.index] = held
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=scores.device)
+    lab = torch.empty((B, H, W), dtype=torch.int64, device=scores.device) if return_map else None
+    _lib.check(lib.dml_crf_gauss(scores.data_ptr(), conf.data_ptr(), lab.data_ptr() if return_map else None,
+                                 held[1].data_ptr(), B, K, H, W, int(first_class), float(sx), float(sy), float(compat),
+                                 int(iters), float(clip), _st(scores)), "dml_crf_gauss")
+    return (conf, lab) if return_map else conf
 
 
 def mean_prototype(shots) -> np.ndarray:
