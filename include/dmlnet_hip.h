@@ -628,6 +628,37 @@ int64_t dml_crf_gauss_workspace_bytes(int B, int C, int H, int W);
 int dml_crf_gauss(const float* logits, float* conf, int64_t* map, void* work, int B, int K, int H, int W, int k_first,
                   float sx, float sy, float compat, int iters, float clip, void* stream);
 
+/* Reconstruction-consistency score (anomaly/eval_ood_rec.py:90-150 of the reference, `--ood rec`), in two calls.
+ *
+ * dml_rec_cosine: f1[s], f2[s], s < n (1..DML_REC_MAX_SCALES; host arrays of device pointers), are the decoder's pyramid concats
+ * of the n resized copies of a frame and of its reconstruction, [B, h[s], w[s], C] channels last with a pixel pitch of ld[s] >= C
+ * elements of `dtype` (h, w, ld: host arrays).  With R_s the bilinear resize to (Hq, Wq) of F.interpolate(mode='bilinear',
+ * align_corners=False) (dml_bilinear_fwd's source-index arithmetic; a scale may be larger or smaller than the output):
+ *   a_k = (1/n) sum_s R_s f_k[s]                u_k = a_k / max(|a_k|, 1e-12)                               (F.normalize, dim = C)
+ *   cos[b,y,x] = sum_c (u_1 / max(|u_1|, 1e-8)) (u_2 / max(|u_2|, 1e-8))                                   (F.cosine_similarity)
+ * A pixel where a_1 or a_2 is all zero gives exactly 0, never NaN.  cos: [B, Hq, Wq] fp32.
+ * One launch, no workspace, nothing of size C Hq Wq: a workgroup owns 16 output pixels of one row, a thread 4 channels of each
+ * 1024-channel chunk; the scales are summed per pixel and channel in fp32 registers (a source column, blended over the two source
+ * rows, is loaded once per strip), and only the sums a_1.a_2, |a_1|^2, |a_2|^2 are kept, per thread in LDS, folded in a fixed order at
+ * the end.  No atomics: bitwise reproducible.  Loads of 4 channels (16 bytes of fp32, 8 bytes of bf16) when every ld[s] % 4 == 0
+ * and every pointer is aligned to that load, with the C % 4 last channels one by one; otherwise one channel per load.  Any C >= 1.
+ * DML_EINVAL: a NULL pointer (the arrays, their first n entries, cos), n outside 1..DML_REC_MAX_SCALES, B, C, Hq, Wq, h[s], w[s] <= 0,
+ * ld[s] < C, dtype neither DML_F32 nor DML_BF16.  DML_EUNSUPPORTED: B h[s] w[s] ld[s] (the kernel's element offsets are
+ * 32-bit) or B Hq ceil(Wq / 16) >= 2^31.
+ *
+ * dml_rec_confidence: scores [B, K, H, W] fp32 (the multi-scale mean of the frame's scores), cos [B, Hq, Wq] -> conf [B, H, W]:
+ *   msp = max_c scores[:, c], k_first <= c < K (prob_logit = 1: the reference's statement on its un-softmaxed scores)
+ *       = max_c softmax_c(scores[:, k_first:])  (prob_logit = 0)
+ *   conf = msp > threshold ? msp : (bilinear resize of cos to (H, W))[y, x]
+ * One launch, one thread per pixel: the scores are read once, cos through its four taps.  k_first = 1 is --exclude_back without a
+ * copy.  DML_EINVAL: a NULL pointer, B, K, H, W, Hq, Wq <= 0, k_first < 0 or >= K, K - k_first > 32.  DML_EUNSUPPORTED: B H W or
+ * B Hq Wq > 2^40.  Nothing is launched when a code is returned. */
+#define DML_REC_MAX_SCALES 8
+int dml_rec_cosine(const void* const* f1, const void* const* f2, const int* h, const int* w, const int* ld, int n, int B, int C,
+                   int dtype, float* cos, int Hq, int Wq, void* stream);
+int dml_rec_confidence(const float* scores, const float* cos, float* conf, int B, int K, int H, int W, int Hq, int Wq, int k_first,
+                       float threshold, int prob_logit, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DML loss = CE(-dist^2)/n + alpha * VAR/n (anomaly/models/models.py:42-78; live part of
  * utils/loss.py:34-42 is alpha = 0).

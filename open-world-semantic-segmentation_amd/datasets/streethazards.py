@@ -6,7 +6,9 @@ decode threads only runs `Image.open(...).convert('RGB')` / `Image.open(segm)` i
 the copy to the device goes on a copy stream, and the compute stream waits on its event before one launch of
 dml_pil_resize_normalize writes all scales (bit for bit the reference's tensors, utils/image_resize.py) and
 dml_segm_to_label writes `segm - 1`.  `StreetHazardsReader` yields `(img_resized_list, seg_label)` on the device in list
-order -- what `eval_ood_traditional.evaluate` consumes.
+order -- what `eval_ood_traditional.evaluate` consumes.  With `rec_dataset` the image comes from a second tree of
+reconstructed frames (dataset.py:255-257,272-273: `rec_dataset/<last folder>/<file name>` of `fpath_img`, resized to the
+annotation's size with Pillow NEAREST when it differs); `eval_ood_rec.py` zips such a reader with a plain one.
 """
 from __future__ import annotations
 
@@ -92,8 +94,9 @@ class StreetHazardsReader:
     img_resized_list: fp32 [1, 3, H_s, W_s] per target size; seg_label: int64 [H, W] = annotation - 1."""
 
     def __init__(self, root_dataset, odgt, img_sizes=IMG_SIZES, img_max_size=IMG_MAX_SIZE,
-                 padding_constant=PADDING_CONSTANT, workers=None, device=None, max_sample=-1):
+                 padding_constant=PADDING_CONSTANT, workers=None, device=None, max_sample=-1, rec_dataset=None):
         self.root_dataset = root_dataset
+        self.rec_dataset = rec_dataset        # the images of this tree, the annotations of root_dataset (dataset.py:255-260)
         self.records = parse_odgt(odgt, max_sample=max_sample)
         self.img_sizes = tuple(int(s) for s in img_sizes)
         self.img_max_size = img_max_size
@@ -112,7 +115,13 @@ class StreetHazardsReader:
         from PIL import Image
         t0 = time.perf_counter()
         segm = Image.open(os.path.join(self.root_dataset, rec["fpath_segm"]))
-        img = Image.open(os.path.join(self.root_dataset, rec["fpath_img"])).convert("RGB")
+        if self.rec_dataset:
+            folder_name, image_name = rec["fpath_img"].split("/")[-2:]
+            img = Image.open(os.path.join(self.rec_dataset, folder_name, image_name)).convert("RGB")
+            if img.size != segm.size:
+                img = img.resize(segm.size, Image.NEAREST)           # imresize(img, segm.size, interp='nearest'), :273
+        else:
+            img = Image.open(os.path.join(self.root_dataset, rec["fpath_img"])).convert("RGB")
         assert segm.mode == "L"
         assert img.size[0] == segm.size[0]
         assert img.size[1] == segm.size[1]

@@ -115,6 +115,7 @@ class PredictHead(C.Structure):
 
 
 PREDICT_MAX_HEADS = 4
+REC_MAX_SCALES = 8     # DML_REC_MAX_SCALES
 
 
 class ScaleWindow(C.Structure):
@@ -196,6 +197,8 @@ _PROTOS = {
     "dml_knn_cosine_score": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_crf_gauss_workspace_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
     "dml_crf_gauss": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_p]),
+    "dml_rec_cosine": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
+    "dml_rec_confidence": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dml_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_p]),
     "dml_loss_finalize": (c_i, [c_p, c_p, c_f, c_f, c_p]),
     "dml_loss_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_p]),

@@ -61,6 +61,7 @@ class PPMPlan(Plan):
                 out = cat.slice(0, fc_dim)
             x = self.cbr(u2.z, blk.conv3, blk.bn3, relu=True, res=idt, out=out).z
         conv5, h, w = x, x.H, x.W
+        self.cat = cat          # the pyramid concat [B, h, w, fc_dim + 512 n_ppm]: infer_multiscale(keep_cat=True) copies it out
 
         # pyramid pooling (models.py:620-631): AdaptiveAvgPool2d(s) -> 1x1 conv -> BN -> ReLU -> bilinear back to h x w
         for i, branch in enumerate(dec.ppm):
@@ -121,11 +122,11 @@ class PPMEngine(Engine):
         plan.refresh_weights(torch.cuda.current_stream(x.device).cuda_stream)
         B = x.shape[0]
         Hs, Ws = int(seg_size[0]), int(seg_size[1])
-        for t in (scores, feats):
+        for t in (scores, feats) if scores is not None else ():
             if tuple(t.shape) != (B, plan.K, Hs, Ws) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
                 raise ValueError("accumulators must be contiguous float32 [B, %d, %d, %d] on the input's device" % (plan.K, Hs, Ws))
         plan.images_args[0] = x.data_ptr()
-        for args, dst in ((plan.up_scores, scores), (plan.up_feats, feats)):
+        for args, dst in ((plan.up_scores, scores), (plan.up_feats, feats)) if scores is not None else ():
             args[1], args[7], args[8], args[9], args[10] = dst.data_ptr(), Hs, Ws, float(alpha), 1 if accumulate else 0
         plan.last_input = x
         return plan
@@ -164,16 +165,22 @@ class PPMEngine(Engine):
             plan._static_in.copy_(x)
             plan._graph.replay()
 
-    def infer_multiscale(self, imgs, seg_size, dtype: torch.dtype):
+    def infer_multiscale(self, imgs, seg_size, dtype: torch.dtype, keep_cat: bool = False, want_scores: bool = True):
         """eval_ood_traditional.py:190-210 for the resized copies of one frame: scores = sum_i pred_i / n (same for the
         features).  The copies are small (grids of 40-200 workgroups), so their plans run CONCURRENTLY, one HIP stream
-        each; only the two upsample-accumulate launches of every scale are ordered, on the caller's stream."""
+        each; only the two upsample-accumulate launches of every scale are ordered, on the caller's stream.
+        keep_cat=True returns (scores, feats, cats): cats[i] is the pyramid concat of imgs[i], [B, h_i, w_i, C] in the plan's
+        dtype, a copy the caller owns (made on the scale's stream behind its body: a plan's buffers are rewritten by the
+        next frame of the same shape, and the captured graph has their addresses baked in).  want_scores=False skips the
+        upsample-accumulate launches and returns None for scores and feats (eval_ood_rec.py never reads the
+        reconstruction's)."""
         n = len(imgs)
         dev = imgs[0].device
         main = torch.cuda.current_stream(dev)
         shape = (imgs[0].shape[0], 13, int(seg_size[0]), int(seg_size[1]))
-        scores = torch.empty(shape, dtype=torch.float32, device=dev)
-        feats = torch.empty(shape, dtype=torch.float32, device=dev)
+        scores = torch.empty(shape, dtype=torch.float32, device=dev) if want_scores else None
+        feats = torch.empty(shape, dtype=torch.float32, device=dev) if want_scores else None
+        cats = [None] * n
         if not hasattr(self, "_scale_streams"):
             self._scale_streams = {}
         pool = self._scale_streams.setdefault(dev, [])
@@ -189,15 +196,20 @@ class PPMEngine(Engine):
                 seen.add(tuple(imgs[i].shape))
                 plan = self._prepare(imgs[i], seg_size, dtype, scores, feats, 1.0 / n, True)
                 # snapshot the per-call arguments of the tail (a later wave re-patches the same lists)
-                tail = [(fn, list(args)) for fn, args in plan.fwd[-2:]]
-                wave.append((plan, tail, pool[len(wave)]))
-            for plan, tail, s in wave:
+                tail = [(fn, list(args)) for fn, args in plan.fwd[-2:]] if want_scores else []
+                wave.append((plan, tail, pool[len(wave)], i))
+            for plan, tail, s, i in wave:
                 s.wait_stream(main)
                 if self.use_graphs:
                     self._replay_body(plan, s)
                 else:
                     Plan.run(plan.fwd, s.cuda_stream, 0, len(plan.fwd) - 2)
-            for plan, tail, s in wave:
+                if keep_cat:
+                    c = plan.cat
+                    with torch.cuda.stream(s):
+                        cats[i] = c.t.view(c.B, c.H, c.W, c.ld)[..., :c.C].clone()
+                    cats[i].record_stream(main)          # allocated on the scale's stream, read on the caller's
+            for plan, tail, s, i in wave:
                 main.wait_stream(s)
                 for fn, args in tail:
                     args[10] = 0 if first else 1
@@ -206,4 +218,4 @@ class PPMEngine(Engine):
                         _lib.check(rc, "upsample-accumulate")
                 first = False
             todo = later
-        return scores, feats
+        return (scores, feats, cats) if keep_cat else (scores, feats)

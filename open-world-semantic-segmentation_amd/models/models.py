@@ -196,3 +196,29 @@ def evaluate_multiscale(segmentation_module, img_resized_list, segSize):
         raise NotImplementedError("only the inference branch (eval(), decoder built with use_softmax=True) runs on the MI355X path")
     with torch.no_grad():
         return m._engine.infer_multiscale(list(img_resized_list), segSize, m._dtype)
+
+
+def evaluate_multiscale_rec(segmentation_module, img_resized_list, img_resized_list_rec, segSize):
+    """The two loops of anomaly/eval_ood_rec.py:102-125 and its :143-146 for one frame and its reconstruction ->
+    (scores [B, 13, H, W], cos [B, int(H / 4), int(W / 4)]).  scores is evaluate_multiscale's multi-scale mean of the
+    frame; cos compares the decoder's pyramid concat (`ft = ppm_out.clone()`, models.py:632 of the reference: 4096
+    channels) of the frame with that of the reconstruction, each averaged over the scales at a quarter of segSize
+    (utils.rec_cosine_score reads the per-scale concats directly; the reference's two 4096 x H/4 x W/4 accumulators are
+    never formed).  The reconstruction's scores and embeddings are not computed."""
+    import utils
+    m = segmentation_module
+    if m.training or not m.decoder.use_softmax:
+        raise NotImplementedError("only the inference branch (eval(), decoder built with use_softmax=True) runs on the MI355X path")
+    imgs, recs = list(img_resized_list), list(img_resized_list_rec)
+    if len(imgs) != len(recs) or not imgs:
+        raise ValueError("the frame and its reconstruction need the same, non-zero number of resized copies (%d / %d)"
+                         % (len(imgs), len(recs)))
+    for a, b in zip(imgs, recs):
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError("a resized copy of the reconstruction has shape %s where the frame's has %s"
+                             % (tuple(b.shape), tuple(a.shape)))
+    with torch.no_grad():
+        scores, _, cats = m._engine.infer_multiscale(imgs, segSize, m._dtype, keep_cat=True)
+        _, _, cats_rec = m._engine.infer_multiscale(recs, segSize, m._dtype, keep_cat=True, want_scores=False)
+        cos = utils.rec_cosine_score(cats, cats_rec, (int(segSize[0] / 4), int(segSize[1] / 4)))
+    return scores, cos

@@ -129,6 +129,95 @@ def dense_crf_gauss(scores: torch.Tensor, sxy=3.0, compat: float = 3.0, iters: i
     return (conf, lab) if return_map else conf
 
 
+def _nhwc_pitch(t):
+    """the pixel pitch, in elements, of a [B, h, w, C] tensor that is dense but for that pitch (a channel slice of a wider
+    buffer), or None for any other layout; dimensions of size 1 do not count"""
+    B, h, w, C = t.shape
+    if C > 1 and t.stride(3) != 1:
+        return None
+    ld = None
+    for size, dim, pixels in ((w, 2, 1), (h, 1, w), (B, 0, h * w)):
+        if size > 1:
+            if ld is None:
+                if t.stride(dim) % pixels:
+                    return None
+                ld = t.stride(dim) // pixels
+            elif t.stride(dim) != pixels * ld:
+                return None
+    ld = C if ld is None else ld
+    return ld if ld >= C else None
+
+
+def rec_cosine_score(feats1, feats2, out_hw) -> torch.Tensor:
+    """The cosine map of anomaly/eval_ood_rec.py:96-125,143-146 of the reference (dml_rec_cosine): feats1[s] / feats2[s]
+    are the pyramid concats of the s-th resized copy of a frame and of its reconstruction, [B, h_s, w_s, C] channels last,
+    fp32 or bf16 (a channel slice of a wider buffer is taken as it is).  Each list is resized bilinearly to out_hw
+    (F.interpolate, align_corners=False) and averaged, the two means are normalised over the channels and compared by
+    F.cosine_similarity -> [B, Hq, Wq] fp32; a pixel where either mean is all zero gives 0.  One launch; nothing of the
+    size C x Hq x Wq is allocated."""
+    import ctypes
+    feats1, feats2 = list(feats1), list(feats2)
+    n = len(feats1)
+    if n == 0 or len(feats2) != n:
+        raise ValueError("feats1 and feats2 must be two lists of the same, non-zero length")
+    if n > _lib.REC_MAX_SCALES:
+        raise ValueError("at most %d scales" % _lib.REC_MAX_SCALES)
+    for t in feats1 + feats2:
+        _need_cuda(t)
+    dtype, dev = feats1[0].dtype, feats1[0].device
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("the concats must be float32 or bfloat16, not %s" % (dtype,))
+    B, C = feats1[0].shape[0], feats1[0].shape[-1]
+    keep, geo = [], []
+    for a, b in zip(feats1, feats2):
+        if a.dim() != 4 or a.shape != b.shape or a.shape[0] != B or a.shape[-1] != C:
+            raise ValueError("every scale needs two [B, h, w, C] tensors of one shape: %s / %s" % (tuple(a.shape), tuple(b.shape)))
+        if a.dtype != dtype or b.dtype != dtype or a.device != dev or b.device != dev:
+            raise ValueError("the concats must share one dtype and one device")
+        _, h, w, _ = a.shape
+        ld = _nhwc_pitch(a)
+        pair = [a, b]
+        if ld is None or _nhwc_pitch(b) != ld:         # one pitch for both inputs of a scale
+            pair, ld = [a.contiguous(), b.contiguous()], C
+        keep.extend(pair)
+        geo.append((h, w, ld))
+    lib = _lib.load()
+    Hq, Wq = int(out_hw[0]), int(out_hw[1])
+    cos = torch.empty((B, Hq, Wq), dtype=torch.float32, device=dev)
+    p1 = (ctypes.c_void_p * n)(*[t.data_ptr() for t in keep[0::2]])
+    p2 = (ctypes.c_void_p * n)(*[t.data_ptr() for t in keep[1::2]])
+    hs, ws, lds = ((ctypes.c_int * n)(*[g[i] for g in geo]) for i in range(3))
+    _lib.check(lib.dml_rec_cosine(p1, p2, hs, ws, lds, n, B, C, _lib.DML_BF16 if dtype == torch.bfloat16 else _lib.DML_F32,
+                                  cos.data_ptr(), Hq, Wq, _st(cos)), "dml_rec_cosine")
+    return cos
+
+
+def rec_confidence(scores: torch.Tensor, cos: torch.Tensor, threshold: float = 0.999, prob: str = "logit",
+                   first_class: int = 0) -> torch.Tensor:
+    """The confidence of anomaly/eval_ood_rec.py:127-150 of the reference (dml_rec_confidence): scores [B, K, H, W] fp32,
+    cos [B, Hq, Wq] (rec_cosine_score) -> conf [B, H, W] = msp where msp > threshold, else cos resized bilinearly to
+    (H, W).  msp is the maximum over the classes first_class .. K - 1 (first_class=1 is --exclude_back without a copy) of
+    the scores themselves for prob="logit" or of their softmax for prob="softmax".  "logit" is the reference's literal
+    statement: its scores are negative squared distances, never above 0, so with the reference's threshold of 0.999 the
+    gate never opens and conf is the resized cosine map alone; "softmax" is what the name msp and the 0.999 intend."""
+    _need_cuda(scores)
+    _need_cuda(cos)
+    if scores.dim() != 4 or cos.dim() != 3 or cos.shape[0] != scores.shape[0]:
+        raise ValueError("scores must be [B, K, H, W] and cos [B, Hq, Wq]")
+    if prob not in ("softmax", "logit"):
+        raise ValueError("prob must be 'softmax' or 'logit', not %r" % (prob,))
+    if scores.dtype != torch.float32 or cos.dtype != torch.float32:
+        raise TypeError("scores and cos must be float32")
+    lib = _lib.load()
+    scores, cos = scores.contiguous(), cos.contiguous()
+    B, K, H, W = scores.shape
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=scores.device)
+    _lib.check(lib.dml_rec_confidence(scores.data_ptr(), cos.data_ptr(), conf.data_ptr(), B, K, H, W, cos.shape[1], cos.shape[2],
+                                      int(first_class), float(threshold), 1 if prob == "logit" else 0, _st(scores)),
+               "dml_rec_confidence")
+    return conf
+
+
 def mean_prototype(shots) -> np.ndarray:
     """test_embedding.py:254-257."""
     return np.mean(np.asarray(shots, dtype=np.float64), axis=0)
