@@ -476,11 +476,28 @@ int dml_bilinear_bwd(const void* dy, void* dx, int B, int h, int w, int H, int W
  * ---------------------------------------------------------------------------------------------- */
 /* x: embedding at full resolution, NCHW fp32 (what F.interpolate returns at utils.py:88).
  * logits[b,k,h,w] = -sum_c (x[b,c,h,w]-protos[k][c])^2 (NCHW), features_out = x in NHWC.
- * Any of logits / feats / argmax / dissum may be NULL.  192 B per pixel at K=C=16. */
+ * Any of logits / feats / argmax / dissum may be NULL.  192 B per pixel at K=C=16.
+ *   feats    a copy of x, bit for bit (-0.0 and NaN payloads included).
+ *   argmax   [B,H,W] uint8: the FIRST k with the largest logit (strict > against a running best that starts at -inf, k = 0).  A NaN
+ *            logit therefore never wins, and a pixel with no logit above -inf (all NaN or -inf: a NaN or inf feature) reports 0.
+ *   dissum   [B,H,W] = -sum_k logits[b,k,h,w], the kernel's own fp32 logits summed in k order.
+ *   inf / NaN features propagate: every logit and the dissum of that pixel are -inf / +inf or NaN; other pixels are not touched.
+ * Supported: 1 <= C <= 32, 1 <= K <= 33 (DML_EUNSUPPORTED otherwise); x or protos NULL, B / H / W <= 0: DML_EINVAL.  Nothing is
+ * launched when a code is returned.
+ * Alignment (assumed, not checked): with H*W % 4 == 0 a lane owns four consecutive pixels and x, logits and dissum are accessed as
+ * 16-byte vectors -- they must be 16-byte aligned; with C % 4 == 0 a pixel's features are stored as 16-byte vectors -- feats must be
+ * 16-byte aligned.  Otherwise 4-byte alignment is enough.  argmax has no alignment requirement. */
 int dml_proto_dist_fwd(const float* x_nchw, const float* protos, float* logits, float* feats,
                        uint8_t* argmax, float* dissum, int B, int C, int K, int H, int W, void* stream);
 /* Fused: bilinear x(H/h) upsample of the low-resolution embedding e[B,h,w,C] (NHWC fp32) + the
- * distance head, writing logits NCHW and features_out NHWC at [H,W]. */
+ * distance head, writing logits NCHW and features_out NHWC at [H,W].
+ *   feats = F.interpolate(e, (H,W), bilinear, align_corners = False) in fp32 (any ratio, shrinking included); logits, argmax (first
+ *   maximum, NaN never wins) and dissum as dml_proto_dist_fwd defines them, on those features.  Any of the four outputs may be NULL.
+ *   A non-finite value of e makes the output pixels that interpolate it non-finite; which pixels next to those also become NaN
+ *   (a zero weight times inf) is not part of the contract.
+ * Supported C, K and the codes: as dml_proto_dist_fwd, with h / w <= 0 refused as well.
+ * Alignment (assumed, not checked): with W % 4 == 0 logits and dissum are written as 16-byte vectors and must be 16-byte aligned; with
+ * C % 4 == 0 e is read and feats is written as 16-byte vectors and both must be 16-byte aligned. */
 int dml_upsample_dist_fwd(const float* e, const float* protos, float* logits, float* feats,
                           uint8_t* argmax, float* dissum, int B, int h, int w, int C, int K, int H,
                           int W, void* stream);
@@ -509,7 +526,11 @@ typedef struct DmlPredictHead {
 } DmlPredictHead;
 int dml_incremental_predict(const DmlPredictHead* heads, int n, int64_t* preds, uint8_t* head_argmax, int B, int h, int w,
                             int H, int W, void* stream);
-/* df[b,h,w,c] = -2 * sum_k glogits[b,k,h,w] * (feats[b,h,w,c]-protos[k][c]) (+ gfeats[b,h,w,c]) */
+/* df[b,h,w,c] = -2 * sum_k glogits[b,k,h,w] * (feats[b,h,w,c]-protos[k][c]) (+ gfeats[b,h,w,c]); gfeats may be NULL.
+ * Evaluated as -2 (gs f - gm) with gs = sum_k g_k and gm_c = sum_k g_k protos[k][c]: a pixel whose g_k are all zero gets
+ * df = gfeats (or 0).  1 <= C <= 32, 1 <= K <= 33 (DML_EUNSUPPORTED otherwise); glogits, feats, protos or df NULL, B / H / W <= 0:
+ * DML_EINVAL, before any launch.  Alignment (assumed, not checked): glogits 16-byte aligned when H*W % 4 == 0; feats, gfeats and df
+ * 16-byte aligned when C % 4 == 0. */
 int dml_proto_dist_bwd(const float* glogits, const float* gfeats, const float* feats,
                        const float* protos, float* df, int B, int C, int K, int H, int W, void* stream);
 
@@ -837,8 +858,11 @@ int64_t dml_adaptive_avgpool_ws_elems(int B, int H, int W, int C, int S);
 int dml_adaptive_avgpool_fwd(const void* x, void* y, float* ws, int B, int H, int W, int C, int ldx, int S,
                              int dtype, void* stream);
 /* out[m][k] = -sum_c (emb[m][c] - protos[k][c])^2 for k < K on an NHWC fp32 embedding with Kp (<= 32) channels
- * (pad channels zero in emb and protos[K][Kp]); out channels K..Kp-1 = 0.  models.py:633-657: the distance is
- * taken at 1/8 resolution, BEFORE the upsample. */
+ * (pad channels zero in emb and protos[K][Kp]); out channels K..Kp-1 = +0.0.  models.py:633-657: the distance is
+ * taken at 1/8 resolution, BEFORE the upsample.  Rows of emb have pitch lde and rows of out pitch ldo (both >= Kp): columns Kp..lde-1
+ * are never read and columns Kp..ldo-1 never written.  Scalar accesses: 4-byte alignment is enough.
+ * DML_EINVAL: a NULL pointer, M <= 0, K <= 0, K > 33, Kp < 1, Kp > 32, K > Kp + 1, lde < Kp or ldo < Kp; DML_EUNSUPPORTED: K == Kp + 1
+ * (one output channel per prototype inside the padded width). */
 int dml_proto_dist_nhwc(const float* emb, const float* protos, float* out, int64_t M, int K, int Kp, int lde,
                         int ldo, void* stream);
 /* dst[B,C,H,W] (+)= alpha * bilinear(src[B,h,w,ld] channels 0..C-1), align_corners = False -- F.interpolate to

@@ -1639,7 +1639,7 @@ extern "C" int dml_incremental_predict(const DmlPredictHead* heads, int n, int64
 extern "C" int dml_proto_dist_bwd(const float* glogits, const float* gfeats, const float* feats,
                                   const float* protos, float* df, int B, int C, int K, int H, int W,
                                   void* stream) {
-    if (!glogits || !feats || !protos || !df) return DML_EINVAL;
+    if (!glogits || !feats || !protos || !df || B <= 0 || H <= 0 || W <= 0) return DML_EINVAL;
     if (C <= 0 || C > MAXC || K <= 0 || K > MAXK) return DML_EUNSUPPORTED;
     const int64_t HW = (int64_t)H * W;
     hipStream_t st = static_cast<hipStream_t>(stream);
