@@ -730,6 +730,47 @@ int dml_focal_loss_bwd(const float* logits, const int64_t* labels, const double*
                        int size_average, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Feature-distillation term (utils/loss.py:104-117 of the reference, main_distillation.py:427-434) of teacher features
+ * t[B,H,W,Ct] and student features s[B,H,W,Cs], both fp32, channels last, dense, 1 <= Ct <= Cs <= 32, and labels[B,H,W] int64.
+ * pad(t) is t with zero channels appended up to Cs (the reference appends one).  A pixel is masked in when its label != novel_id
+ * -- a label equal to ignore_index is therefore masked in, as in the reference after its fill.  Per image i
+ *   S_i = sum over masked-in pixels and all Cs channels of (s - pad(t))^2      cnt_i = #masked-in pixels
+ *   dis = (1 / n) sum_{i: cnt_i > 0} S_i / cnt_i       d dis / d s[i,p,c] = 2 / (n cnt_i) (s - pad(t)) on a masked-in pixel, else 0
+ * An image with cnt_i = 0 contributes 0 and has a zero gradient; the reference divides by zero there and returns NaN.
+ * DML_EINVAL (nothing is launched): a NULL pointer other than t_logits, gout (and labels_out when t_logits is NULL), B, H or
+ * W <= 0, Ct < 1, Ct > Cs, Cs > 32.  DML_EUNSUPPORTED (nothing is launched): B > 2048, or H W Cs >= 2^31 (offsets inside one
+ * image are 32-bit, the image's base offset is 64-bit).
+ * An image's student tensor is taken flat in groups of four floats, one lane each, with the group's (up to four, consecutive)
+ * teacher floats and the one or two labels it touches: 16-byte loads and stores of s (and gs) when H W Cs % 4 == 0 and they are
+ * 16-byte aligned, one float at a time otherwise; a group sees the same operations in the same order on either path (bitwise
+ * equal results).  t, labels and t_logits need their natural alignment only.  Grid-stride loops.  No atomics: bitwise
+ * reproducible.
+ *
+ * dml_distill_fwd: one pass.  With t_logits ([B,Ct,H,W], NCHW; the teacher's logits) not NULL it also writes
+ *   labels_out[p] = labels_in[p] == ignore_index ? first maximal k of t_logits[:, p] : labels_in[p]
+ * (the tie rule of dml_argmax_msp) and takes the mask from labels_out; labels_out may equal labels_in.  With t_logits == NULL the
+ * labels are only read, ignore_index is unused and labels_out may be NULL.
+ * Launch shape, min(.., 2048 / B) workgroups of 256 lanes per image: without t_logits a workgroup strides over the image's
+ * ceil(H W Cs / 4) groups; with them over its tiles of 256 pixels -- a lane fills one pixel's label (label and logits coalesced
+ * over the tile) and leaves it in LDS, then the tile's 64 Cs groups go over the lanes.
+ * sums (device, double[2 B + 2]): sums[2 i] = S_i, sums[2 i + 1] = cnt_i, sums[2 B] = sum_{i: cnt_i > 0} S_i / cnt_i,
+ * sums[2 B + 1] = B.  fp32 per lane, per-wave and per-workgroup partials in block_partials (2 x 2048 floats, device: a sum and
+ * the bits of an integer count for each workgroup), then one workgroup folds them in double in a fixed order.
+ * ---------------------------------------------------------------------------------------------- */
+int dml_distill_fwd(const float* t_logits, const float* t, const float* s, const int64_t* labels_in, int64_t* labels_out,
+                    double* sums, float* block_partials, int B, int Ct, int Cs, int H, int W, int64_t ignore_index,
+                    int64_t novel_id, void* stream);
+/* *dis (device float) = sums[2 B] / n.  n = n_images, or for n_images <= 0 (here and in dml_distill_bwd) sums[2 B + 1] read on the
+ * device -- the convention of dml_loss_finalize: a data-parallel caller all-reduces the last two doubles and never brings the
+ * count to the host. */
+int dml_distill_finalize(const double* sums, int B, float n_images, float* dis, void* stream);
+/* gs[B,H,W,Cs] = gout * d dis / d s: gout 2 / (n cnt_b) (s - pad(t)) on the masked-in pixels of an image with cnt_b > 0 and exactly
+ * 0 elsewhere; every element is written.  labels: the ones the forward took its mask from (labels_out after a fill).  cnt_b is
+ * read from sums[2 b + 1]; gout is a device scalar, NULL = 1. */
+int dml_distill_bwd(const float* t, const float* s, const int64_t* labels, const double* sums, const float* gout, float* gs,
+                    int B, int Ct, int Cs, int H, int W, int64_t novel_id, float n_images, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SGD with momentum and weight decay, torch semantics (main_embedding.py:385-388):
  *   g = gscale*g + wd*p ; v = mu*v + g ; p -= lr*v
  * ---------------------------------------------------------------------------------------------- */

@@ -17,6 +17,7 @@ DML_F32, DML_BF16 = 0, 1
 STAT_ROWS = 64
 LOSS_BLOCKS = 2048
 FOCAL_PARTIALS = 3 * 2048     # floats of dml_focal_loss_fwd's block_partials
+DISTILL_PARTIALS = 2 * 2048   # floats of dml_distill_fwd's block_partials
 
 c_p = C.c_void_p
 c_i = C.c_int
@@ -205,6 +206,9 @@ _PROTOS = {
     "dml_focal_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_p]),
     "dml_focal_loss_finalize": (c_i, [c_p, c_p, c_i, c_p]),
     "dml_focal_loss_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_i, c_p]),
+    "dml_distill_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_i64, c_p]),
+    "dml_distill_finalize": (c_i, [c_p, c_i, c_f, c_p, c_p]),
+    "dml_distill_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_f, c_p]),
     "dml_sgd_step": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_p]),
     "dml_fill_f32": (c_i, [c_p, c_i64, c_f, c_p]),
     "dml_convert_dtype": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),

@@ -7,6 +7,8 @@ DMLLoss is the live DCE + VL loss of anomaly/models/models.py:42-78: CE/n + alph
 Both run dml_loss_fwd / dml_loss_bwd (one fused pass each instead of a per-image per-class Python loop).
 FocalLoss is utils/loss.py:7-23 there, on dml_focal_loss_fwd / dml_focal_loss_bwd (csrc/focal_loss.hip); the sum reduction
 CrossEntropyLoss(size_average=False) of loss.py:36,42 is that loss with alpha = 1, gamma = 0, divided by the image count.
+CrossEntropyLoss_dis is loss.py:84-122 there with its feature-distillation term (:104-117) on dml_distill_fwd / dml_distill_bwd
+(csrc/distill_loss.hip), off by default as in the reference.
 """
 from __future__ import annotations
 
@@ -173,6 +175,103 @@ class FocalLoss(nn.Module):
             raise ValueError("FocalLoss takes logits [B, K, H, W] with K >= 1, got %s" % (tuple(inputs.shape),))
         return _FocalLossFn.apply(inputs, targets, self.alpha, self.gamma, bool(self.size_average), self.ignore_index,
                                   self.sync)[0]
+
+
+class _DistillFn(torch.autograd.Function):
+    """(student features, teacher features, labels, teacher logits or None) -> (dis, labels the mask was taken from): the labels
+    with their ignored pixels filled when teacher logits are given, the labels themselves otherwise.  Neither the teacher nor
+    the labels are differentiable."""
+
+    @staticmethod
+    def forward(ctx, feats_s, feats_t, target, teacher_logits, ignore_index, novel_id, group):
+        if not feats_s.is_cuda:
+            raise RuntimeError("the distillation loss runs on the HIP path only (no CPU fallback)")
+        lib = _lib.load()
+        s = feats_s.detach().contiguous().float()
+        t = feats_t.detach().contiguous().float()
+        target = target.contiguous().long()
+        if s.dim() != 4 or t.dim() != 4 or s.shape[:3] != t.shape[:3] or tuple(target.shape) != tuple(s.shape[:3]):
+            raise RuntimeError("features [B, H, W, C] of teacher %s and student %s and labels %s do not match"
+                               % (tuple(t.shape), tuple(s.shape), tuple(target.shape)))
+        B, Hh, Ww, Cs = s.shape
+        Ct = t.shape[3]
+        if not 1 <= Ct <= Cs <= 32:
+            raise ValueError("the distillation loss takes 1 <= teacher channels <= student channels <= 32, got %d and %d" % (Ct, Cs))
+        lg_ptr, filled = None, target
+        if teacher_logits is not None:
+            lg = teacher_logits.detach().contiguous().float()
+            if tuple(lg.shape) != (B, Ct, Hh, Ww):
+                raise RuntimeError("teacher logits %s do not match teacher features %s" % (tuple(lg.shape), tuple(t.shape)))
+            lg_ptr, filled = lg.data_ptr(), torch.empty_like(target)
+        sums = torch.empty(2 * B + 2, dtype=torch.float64, device=s.device)
+        part = torch.empty(_lib.DISTILL_PARTIALS, dtype=torch.float32, device=s.device)
+        st = _stream(s)
+        _lib.check(lib.dml_distill_fwd(lg_ptr, t.data_ptr(), s.data_ptr(), target.data_ptr(),
+                                       filled.data_ptr() if lg_ptr is not None else None, sums.data_ptr(), part.data_ptr(),
+                                       B, Ct, Cs, Hh, Ww, int(ignore_index), int(novel_id), st), "dml_distill_fwd")
+        n_images = float(B)
+        if group is not None:
+            import torch.distributed as dist
+            # sum_i S_i / cnt_i and the image count of the global batch: the kernel left both on the device (sums[2B], sums[2B+1]),
+            # so nothing comes to the host and no Python scalar is assigned to a CUDA element (see _DMLLossFn.forward)
+            dist.all_reduce(sums[2 * B:], group=group if group is not True else None)
+            n_images = 0.0
+        dis = torch.empty((), dtype=torch.float32, device=s.device)
+        _lib.check(lib.dml_distill_finalize(sums.data_ptr(), B, n_images, dis.data_ptr(), st), "dml_distill_finalize")
+        ctx.save_for_backward(t, s, filled, sums)
+        ctx.cfg = (int(novel_id), n_images)
+        ctx.mark_non_differentiable(filled)
+        return dis, filled
+
+    @staticmethod
+    def backward(ctx, gout, _gfilled):
+        t, s, filled, sums = ctx.saved_tensors
+        novel_id, n_images = ctx.cfg
+        lib = _lib.load()
+        B, Hh, Ww, Cs = s.shape
+        g = torch.empty_like(s)
+        gout = gout.contiguous().float()
+        _lib.check(lib.dml_distill_bwd(t.data_ptr(), s.data_ptr(), filled.data_ptr(), sums.data_ptr(), gout.data_ptr(),
+                                       g.data_ptr(), B, t.shape[3], Cs, Hh, Ww, novel_id, n_images, _stream(s)),
+                   "dml_distill_bwd")
+        return g, None, None, None, None, None, None
+
+
+class CrossEntropyLoss_dis(nn.Module):
+    """The two-model loss of the reference's main_distillation.py (utils/loss.py:84-122 there): CE(logit, target) / n, plus
+    dis_weight * dis with  dis = (1/n) sum_i (1/cnt_i) sum_{p: target != novel_id} |features_2 - pad(features_1)|^2  -- the
+    feature-distillation term the reference wrote behind an early `return` (:104-117, coefficient 0.01).  dis_weight = 0 (the
+    default) is the reference's live behaviour: the value and gradient of CrossEntropyLoss, bit for bit, and no kernel of
+    csrc/distill_loss.hip is launched.  An image without a masked-in pixel contributes 0 (the reference: NaN).
+
+    forward(logit, target, features_1, features_2, teacher_logits=None): features_1 [B,H,W,Ct] is the teacher's embedding
+    (detached), features_2 [B,H,W,Cs] the student's (the gradient goes there), Ct <= Cs <= 32.  With `teacher_logits`
+    ([B,Ct,H,W]) the ignored pixels of `target` take the teacher's prediction (main_distillation.py:428-430) inside the
+    distillation forward launch, for any dis_weight, and the cross entropy reads the filled labels; `target` itself is not
+    written.  alpha, beta, gamma are accepted and unused, as in the reference.
+    `sync` (True or a process group): the sums of both terms are all-reduced, every rank sees the global batch's loss.
+    The cross entropy's gradient is always materialised: the fused head backward takes no gradient on the features."""
+
+    def __init__(self, alpha=0, beta=0, gamma=0, size_average=True, ignore_index=255, dis_weight=0.0, novel_id=16, sync=None):
+        super().__init__()
+        self.alpha, self.beta, self.gamma = alpha, beta, gamma
+        self.ignore_index, self.size_average, self.sync = ignore_index, size_average, sync
+        self.dis_weight, self.novel_id = float(dis_weight), int(novel_id)
+        if not math.isfinite(self.dis_weight):
+            raise ValueError("CrossEntropyLoss_dis needs a finite dis_weight, got %r" % (dis_weight,))
+        self._ce = CrossEntropyLoss(size_average=size_average, ignore_index=ignore_index, sync=sync)
+
+    def forward(self, logit, target, features_1=None, features_2=None, teacher_logits=None):
+        dis = None
+        if self.dis_weight != 0 or teacher_logits is not None:
+            if features_1 is None or features_2 is None:
+                raise ValueError("CrossEntropyLoss_dis needs features_1 and features_2 for dis_weight != 0 or teacher_logits")
+            if self.dis_weight == 0:
+                features_2 = features_2.detach()                      # the fill alone: nothing reaches the features
+            dis, target = _DistillFn.apply(features_2, features_1, target, teacher_logits, self.ignore_index, self.novel_id,
+                                           self.sync)
+        ce = self._ce(logit, target)
+        return ce if self.dis_weight == 0 else ce + self.dis_weight * dis
 
 
 class CrossEntropyLoss(nn.Module):
