@@ -771,6 +771,62 @@ int dml_distill_bwd(const float* t, const float* s, const int64_t* labels, const
                     int B, int Ct, int Cs, int H, int W, int64_t novel_id, float n_images, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Inter-class and centre terms of the metric loss (utils/loss.py:43-79 of the reference, behind its early return) of logits
+ * L[B,K,H,W] (NCHW; minus the squared distances), features F[B,H,W,C] (channels last, dense) and labels[B,H,W] int64, all fp32,
+ * 1 <= K <= 32, 1 <= C <= 32.  N = H W counts every pixel of an image, the ignored ones too (the reference's total_size, the
+ * divisor of dml_loss_fwd's VAR).  A pixel is valid when its label != ignore_index; a valid label lies in [0, K) (the caller's
+ * duty; a label outside is skipped like an ignored one, never used as an index).  For image i and class c with n_ic >= 1 pixels
+ *   mu_ic    = (1 / n_ic) sum_{p: y_p = c} F[i,p,:]
+ *   Inter_i  = (1 / N) sum_{valid p} sum_{k != y_p} L[i,k,p]
+ *   Center_i = (1 / N) sum_{valid p} |F[i,p,:] - mu_{i,y_p}|^2
+ *   term     = (beta sum_i Inter_i + gamma sum_i Center_i) / n                          n = images of the (global) batch
+ *   d term / d L[i,k,p] = beta / (n N) on a valid pixel for k != y_p, else 0
+ *   d term / d F[i,p,:] = 2 gamma / (n N) (F[i,p,:] - mu_{i,y_p}) on a valid pixel, else 0   (the part through mu cancels)
+ * An image without a valid pixel contributes 0; a class of one pixel contributes 0 to Center.  The features are taken flat over
+ * H W: the reference indexes features_in[i] ([H,W,C]) with flat pixel indices along its first dimension, which fails as soon as a
+ * class has a pixel index >= H; the geometry it intended is the one computed here.
+ * Center is summed from the deviations F - mu in a second read of the features, never as sum |F|^2 - n |mu|^2.
+ * No atomics, in global memory or LDS: bitwise reproducible.  fp32 per lane, then double, in a fixed order.
+ * DML_EINVAL (nothing is launched): a NULL pointer other than the optional ones named below, B, H or W <= 0, K < 1, C < 1, beta
+ * or gamma not finite.  DML_EUNSUPPORTED (nothing is launched): K > 32, C > 32, B > 2048, H W C >= 2^31 (offsets inside an image
+ * are 32-bit, the image's base offset is 64-bit).
+ *
+ * dml_metric_fwd.  logits NULL: Inter_i = 0 and the logits are not read; feats NULL: Center_i = 0, means and counts are not
+ * written (and may be NULL) and C is only range-checked; not both NULL.
+ *   means[B,K,C] fp32 = mu (0 for a class absent from the image), counts[B,K] int32 = n_ic: kept for the backward.
+ *   sums (device, double[2 B + 3]): sums[2 i] = Inter_i, sums[2 i + 1] = Center_i, sums[2 B] = sum_i Inter_i,
+ *   sums[2 B + 1] = sum_i Center_i, sums[2 B + 2] = B.
+ *   work (device, 16-byte aligned): 2048 (2 + K (C + 1)) doubles.
+ * Launches, each min(.., 2048 / B) workgroups of 256 lanes per image:
+ *   1 (with feats) class sums: a wave takes 64 / CP pixels x CP channel lanes per step, CP = C rounded up to a power of two; a lane
+ *     owns one column of a wave-private LDS table [K][64] (plus [K][64 / CP] counts; 4 K (64 + 64 / CP) 4 bytes per workgroup)
+ *     and adds its float into the row of its pixel's label in program order; dword loads, 4 C bytes per pixel contiguous over
+ *     the wave.  The workgroup folds its columns in double into work: K (C + 1) doubles per workgroup.
+ *   2 (with feats) a wave per (class, channel) folds the workgroups' partials in double: means, counts.
+ *   3 the image's means in LDS; the features flat in groups of four floats per lane (the mapping of dml_distill_fwd), fp32 sum of
+ *     (F - mu)^2 per lane; then the logits, four consecutive pixels per lane, plane by plane, fp32 sum of the planes k != y.
+ *     16-byte loads of F when H W C % 4 == 0 and F is 16-byte aligned, of L when H W % 4 == 0 and L is 16-byte aligned, one float
+ *     at a time otherwise; the same lane takes the same elements in the same order on either path (bitwise equal results).
+ *     Two doubles per workgroup into work.
+ *   4 one workgroup folds those in double: a wave per image, then one wave over the images.
+ * ---------------------------------------------------------------------------------------------- */
+int dml_metric_fwd(const float* logits, const float* feats, const int64_t* labels, float* means, int32_t* counts, double* sums,
+                   double* work, int B, int K, int C, int H, int W, int64_t ignore_index, void* stream);
+/* *term (device float) = (beta sums[2 B] + gamma sums[2 B + 1]) / n.  n = n_images, or for n_images <= 0 (here and in
+ * dml_metric_bwd) sums[2 B + 2] read on the device -- the convention of dml_loss_finalize and dml_distill_finalize: a data-parallel
+ * caller all-reduces the last three doubles and never brings the count to the host. */
+int dml_metric_finalize(const double* sums, int B, float beta, float gamma, float n_images, float* term, void* stream);
+/* gfeats[B,H,W,C] (not NULL: feats and means required) = gout 2 gamma / (n N) (F - mu_y) on a valid pixel and exactly 0
+ * elsewhere; every element is written.  glogits[B,K,H,W] (not NULL) += gout beta / (n N) on a valid pixel for k != y_p, in place:
+ * one read-modify-write pass over the buffer dml_loss_bwd has written, from the labels alone; the own-class element of a valid
+ * pixel is rewritten with its own value and a group of four pixels without a valid one is not touched.  Either may be NULL, not
+ * both.  The two weights are rounded to fp32 once.  gout is a device scalar, NULL = 1.  16-byte accesses under the conditions
+ * of the forward (gfeats and glogits 16-byte aligned as well). */
+int dml_metric_bwd(const float* feats, const int64_t* labels, const float* means, const double* sums, const float* gout,
+                   float* glogits, float* gfeats, int B, int K, int C, int H, int W, int64_t ignore_index, float beta, float gamma,
+                   float n_images, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SGD with momentum and weight decay, torch semantics (main_embedding.py:385-388):
  *   g = gscale*g + wd*p ; v = mu*v + g ; p -= lr*v
  * ---------------------------------------------------------------------------------------------- */

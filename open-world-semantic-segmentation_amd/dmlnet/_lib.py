@@ -19,6 +19,12 @@ LOSS_BLOCKS = 2048
 FOCAL_PARTIALS = 3 * 2048     # floats of dml_focal_loss_fwd's block_partials
 DISTILL_PARTIALS = 2 * 2048   # floats of dml_distill_fwd's block_partials
 
+
+def metric_work_doubles(K, C):
+    """doubles of dml_metric_fwd's work"""
+    return 2048 * (2 + K * (C + 1))
+
+
 c_p = C.c_void_p
 c_i = C.c_int
 c_i64 = C.c_int64
@@ -209,6 +215,9 @@ _PROTOS = {
     "dml_distill_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_i64, c_p]),
     "dml_distill_finalize": (c_i, [c_p, c_i, c_f, c_p, c_p]),
     "dml_distill_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_f, c_p]),
+    "dml_metric_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_p]),
+    "dml_metric_finalize": (c_i, [c_p, c_i, c_f, c_f, c_f, c_p, c_p]),
+    "dml_metric_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_f, c_f, c_f, c_p]),
     "dml_sgd_step": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_p]),
     "dml_fill_f32": (c_i, [c_p, c_i64, c_f, c_p]),
     "dml_convert_dtype": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),

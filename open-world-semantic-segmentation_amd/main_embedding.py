@@ -34,6 +34,8 @@ def get_argparser():
     p.add_argument("--crop_size", type=int, default=768)
     p.add_argument("--loss_type", default="cross_entropy", choices=["cross_entropy", "dml", "focal_loss"])
     p.add_argument("--alpha", type=float, default=0.01, help="weight of the variance loss for --loss_type dml")
+    p.add_argument("--beta", type=float, default=0.0, help="weight of the inter-class term for --loss_type dml")
+    p.add_argument("--gamma", type=float, default=0.0, help="weight of the centre term for --loss_type dml")
     p.add_argument("--focal_alpha", type=float, default=1.0, help="alpha of --loss_type focal_loss")
     p.add_argument("--focal_gamma", type=float, default=0.0, help="gamma of --loss_type focal_loss (>= 0)")
     p.add_argument("--ckpt", default=None)
@@ -102,7 +104,8 @@ def main():
         criterion = utils.FocalLoss(ignore_index=255, size_average=True, alpha=opts.focal_alpha, gamma=opts.focal_gamma,
                                     sync=sync)
     elif opts.loss_type == "dml":
-        criterion = utils.DMLLoss(alpha=opts.alpha, ignore_index=255, sync=sync, fused_backward=True)
+        criterion = utils.DMLLoss(alpha=opts.alpha, ignore_index=255, sync=sync, fused_backward=True, beta=opts.beta,
+                                  gamma=opts.gamma)                     # beta or gamma != 0: the gradient is materialised
     else:
         criterion = utils.CrossEntropyLoss(ignore_index=255, alpha=0, beta=0, gamma=0, sync=sync,
                                            fused_backward=True)                                   # :401

@@ -5,6 +5,7 @@ over valid pixels) / n; alpha/beta/gamma are accepted and -- exactly as in the r
 Center terms sit behind an early `return` (loss.py:42-82) -- do not change the value.
 DMLLoss is the live DCE + VL loss of anomaly/models/models.py:42-78: CE/n + alpha * VAR/n.
 Both run dml_loss_fwd / dml_loss_bwd (one fused pass each instead of a per-image per-class Python loop).
+DMLLoss(beta=, gamma=) adds the Inter and Center terms of loss.py:43-79 there on dml_metric_fwd / dml_metric_bwd (csrc/metric_terms.hip).
 FocalLoss is utils/loss.py:7-23 there, on dml_focal_loss_fwd / dml_focal_loss_bwd (csrc/focal_loss.hip); the sum reduction
 CrossEntropyLoss(size_average=False) of loss.py:36,42 is that loss with alpha = 1, gamma = 0, divided by the image count.
 CrossEntropyLoss_dis is loss.py:84-122 there with its feature-distillation term (:104-117) on dml_distill_fwd / dml_distill_bwd
@@ -90,21 +91,121 @@ class _DMLLossFn(torch.autograd.Function):
         return g, None, None, None, None, None
 
 
+class _DMLMetricLossFn(torch.autograd.Function):
+    """CE/n + alpha VAR/n + (beta Inter + gamma Center)/n in one function: dml_loss_fwd + dml_metric_fwd and their finalizes;
+    backward dml_loss_bwd, then dml_metric_bwd adds the Inter gradient into the same buffer and writes the feature gradient."""
+
+    @staticmethod
+    def forward(ctx, logit, target, feats, alpha, beta, gamma, ignore_index, group):
+        if not logit.is_cuda:
+            raise RuntimeError("the DML loss runs on the HIP path only (no CPU fallback)")
+        lib = _lib.load()
+        logit = logit.contiguous().float()
+        target = target.contiguous().long()
+        B, K, H, W = logit.shape
+        if target.shape != (B, H, W):
+            raise RuntimeError("target shape %s does not match logits %s" % (tuple(target.shape), tuple(logit.shape)))
+        if not 1 <= K <= 32:
+            raise ValueError("the Inter and Center terms take 1 <= classes <= 32, got %d" % K)
+        C = 1
+        ctx.feats_dtype = None if feats is None else feats.dtype
+        if gamma != 0:
+            feats = feats.detach().contiguous().float()
+            if feats.dim() != 4 or tuple(feats.shape[:3]) != (B, H, W):
+                raise RuntimeError("features %s are not [B, H, W, C] of logits %s" % (tuple(feats.shape), tuple(logit.shape)))
+            C = feats.shape[3]
+            if not 1 <= C <= 32:
+                raise ValueError("the Center term takes 1 <= channels <= 32, got %d" % C)
+        else:
+            feats = None
+        dev = logit.device
+        sums = torch.empty(5, dtype=torch.float64, device=dev)
+        part = torch.empty(_lib.LOSS_BLOCKS * 4, dtype=torch.float32, device=dev)
+        msums = torch.empty(2 * B + 3, dtype=torch.float64, device=dev)
+        work = torch.empty(_lib.metric_work_doubles(K, C), dtype=torch.float64, device=dev)
+        means = torch.empty((B, K, C), dtype=torch.float32, device=dev) if feats is not None else None
+        counts = torch.empty((B, K), dtype=torch.int32, device=dev) if feats is not None else None
+        st = _stream(logit)
+        _lib.check(lib.dml_loss_fwd(logit.data_ptr(), target.data_ptr(), sums.data_ptr(), part.data_ptr(), B, K, H, W,
+                                    int(ignore_index), st), "dml_loss_fwd")
+        _lib.check(lib.dml_metric_fwd(logit.data_ptr() if beta != 0 else None, None if feats is None else feats.data_ptr(),
+                                      target.data_ptr(), None if feats is None else means.data_ptr(),
+                                      None if feats is None else counts.data_ptr(), msums.data_ptr(), work.data_ptr(), B, K, C, H, W,
+                                      int(ignore_index), st), "dml_metric_fwd")
+        n_images = float(B)
+        if group is not None:
+            import torch.distributed as dist
+            # as in _DMLLossFn.forward: the image count travels with the sums, on the device
+            sums[4:5].copy_(_image_count(dev, B), non_blocking=True)
+            grp = group if group is not True else None
+            dist.all_reduce(sums, group=grp)
+            dist.all_reduce(msums[2 * B:], group=grp)
+            n_images = 0.0
+        both = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(lib.dml_loss_finalize(sums.data_ptr(), both.data_ptr(), float(alpha), n_images, st), "dml_loss_finalize")
+        _lib.check(lib.dml_metric_finalize(msums.data_ptr(), B, float(beta), float(gamma), n_images, both.data_ptr() + 4, st),
+                   "dml_metric_finalize")
+        ctx.save_for_backward(logit, target, sums, msums, feats, means)
+        ctx.cfg = (float(alpha), float(beta), float(gamma), int(ignore_index), n_images)
+        return both[0] + both[1]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logit, target, sums, msums, feats, means = ctx.saved_tensors
+        alpha, beta, gamma, ignore_index, n_images = ctx.cfg
+        lib = _lib.load()
+        B, K, H, W = logit.shape
+        C = 1 if feats is None else feats.shape[3]
+        st = _stream(logit)
+        g = torch.empty_like(logit)
+        gout = gout.contiguous().float()
+        _lib.check(lib.dml_loss_bwd(logit.data_ptr(), target.data_ptr(), sums.data_ptr(), gout.data_ptr(),
+                                    g.data_ptr(), B, K, H, W, ignore_index, alpha, n_images, st), "dml_loss_bwd")
+        gf = torch.empty_like(feats) if feats is not None and ctx.needs_input_grad[2] else None
+        if beta != 0 or gf is not None:
+            _lib.check(lib.dml_metric_bwd(None if gf is None else feats.data_ptr(), target.data_ptr(),
+                                          None if gf is None else means.data_ptr(), msums.data_ptr(), gout.data_ptr(),
+                                          g.data_ptr() if beta != 0 else None, None if gf is None else gf.data_ptr(), B, K, C, H, W,
+                                          ignore_index, beta, gamma, n_images, st), "dml_metric_bwd")
+        if gf is not None and gf.dtype != ctx.feats_dtype:
+            gf = gf.to(ctx.feats_dtype)
+        return g, None, gf, None, None, None, None, None
+
+
 class DMLLoss(nn.Module):
-    """loss = CE/n + alpha*VAR/n, VAR = sum_i (1/HW_i) sum_{valid p} dist^2(p, own prototype).
+    """loss = CE/n + alpha*VAR/n + beta*Inter/n + gamma*Center/n, per image i with N = H W pixels (the ignored ones counted):
+    VAR_i = (1/N) sum_{valid p} dist^2(p, own prototype), Inter_i = (1/N) sum_{valid p} sum_{k != y_p} logit[i,k,p],
+    Center_i = (1/N) sum_{valid p} |features_in[i,p] - mean of features_in[i] over the pixels of class y_p|^2 -- the three terms of
+    the reference's utils/loss.py:43-79.  features_in [B,H,W,C] is taken flat over H W: the reference indexes features_in[i] with
+    flat pixel indices along its first dimension, which fails for an image with a class pixel at index >= H; the geometry it
+    intended is the one computed here.  An image without a valid pixel and a class of one pixel contribute 0 to Center.
+
+    beta = gamma = 0 (the default) is the loss as it was: the same kernels, value and gradient bit for bit, features_in unused.
+    Otherwise dml_metric_fwd / dml_metric_bwd (csrc/metric_terms.hip) run beside dml_loss_fwd / dml_loss_bwd; for gamma != 0
+    features_in is required and receives a gradient, and fused_backward falls back to the materialised logit gradient (the fused
+    head backward takes no gradient on the features), as CrossEntropyLoss(size_average=False) does.
 
     `sync` (True or a process group): sums are all-reduced so that every rank sees the loss of the global
     batch -- the value nn.DataParallel's gather gives the reference (main_embedding.py:466-467)."""
 
-    def __init__(self, alpha=0.01, ignore_index=-1, sync=None, fused_backward=False):
+    def __init__(self, alpha=0.01, ignore_index=-1, sync=None, fused_backward=False, beta=0.0, gamma=0.0):
         super().__init__()
+        beta, gamma = float(beta), float(gamma)
+        if not (math.isfinite(beta) and math.isfinite(gamma)):
+            raise ValueError("DMLLoss needs finite beta and gamma, got beta=%r gamma=%r" % (beta, gamma))
         self.alpha, self.ignore_index, self.sync = alpha, ignore_index, sync
+        self.beta, self.gamma = beta, gamma
         # True: d(loss)/d(logits) is not materialised; valid when this loss is the only consumer of `logit`, as in the
         # reference's drivers (dmlnet/lazy_grad.py)
         self.fused_backward = fused_backward
 
     def forward(self, logit, target, features_in=None):
-        return _DMLLossFn.apply(logit, target, self.alpha, self.ignore_index, self.sync, self.fused_backward)
+        if self.beta == 0 and self.gamma == 0:
+            return _DMLLossFn.apply(logit, target, self.alpha, self.ignore_index, self.sync, self.fused_backward)
+        if self.gamma != 0 and features_in is None:
+            raise ValueError("DMLLoss needs features_in for gamma != 0")
+        return _DMLMetricLossFn.apply(logit, target, features_in if self.gamma != 0 else None, self.alpha, self.beta, self.gamma,
+                                      self.ignore_index, self.sync)
 
 
 class _FocalLossFn(torch.autograd.Function):
