@@ -976,6 +976,30 @@ int dml_upsample_nhwc_to_nchw(const float* src, float* dst, int B, int h, int w,
 int dml_confusion_update(const int64_t* label_true, const int64_t* label_pred, int64_t* hist,
                          int64_t count, int n_classes, void* stream);
 
+/* Open-set prediction and its threshold sweep (anomaly/eval_ood_traditional.py:155-156,227-229,537-549,599-607 and
+ * test_embedding.py:385-386 of the reference: `pred[conf < thre] = unknown`, scored per threshold), all T thresholds in one read of
+ * conf, pred and label (device arrays of n elements).  thresholds (HOST float[T], 1 <= T <= 12, strictly increasing, no NaN) and
+ * out_labels (HOST int64[n_out], 0 <= n_out <= 8, may be NULL when n_out = 0) are read before the call returns.  Per pixel p:
+ *   l = label[p], and l = unknown_id if l is one of out_labels;  q = pred[p]
+ *   j = #{i : conf[p] >= t_i}, compared in float32: a NaN confidence gives j = 0 (unknown at every threshold), +inf gives j = T, and
+ *       a confidence equal to a threshold keeps its prediction
+ *   if 0 <= l < n_classes and 0 <= q < n_classes: cube[l][q][j] += 1, else the pixel is skipped (dml_confusion_update's rule: 255
+ *       and -1 drop out)
+ *   if open_pred: open_pred[p] = conf[p] >= t_{write_idx} ? q : unknown_id, for every pixel, skipped ones included
+ * cube is a device int64[n_classes][n_classes][T + 1] that the call accumulates into (integer atomics: exact, order-free, bitwise
+ * reproducible).  The confusion matrix of threshold i (rows = label, columns = open-set prediction) follows on the host:
+ *   M_i[l][q] = sum_{j > i} cube[l][q][j]                                               for q != unknown_id
+ *   M_i[l][u] = sum_{j > i} cube[l][u][j] + sum_q sum_{j <= i} cube[l][q][j]            for u = unknown_id
+ * cube may be NULL when open_pred is given (the prediction alone; label is then not read and may be NULL too).
+ * 2 <= n_classes <= 33 (32 model classes and unknown: the largest cube, 33 * 33 * 13 uint32 counters, fits a workgroup's LDS),
+ * 0 <= unknown_id < n_classes, write_idx in [0, T) whenever open_pred is given.  DML_EINVAL for any violation, for n < 0, for a NULL
+ * conf, pred or thresholds, for a NULL label with a cube, and when cube and open_pred are both NULL.  Natural alignment is enough
+ * (4 bytes for conf, 8 for the int64 arrays; DML_EALIGN otherwise).  n == 0 returns 0 and writes nothing; DML_EUNSUPPORTED
+ * from about 2^41 pixels on (a workgroup's 32-bit counters).  No workspace, no host synchronisation. */
+int dml_open_set_sweep(const float* conf, const int64_t* pred, const int64_t* label, int64_t n, const float* thresholds, int T,
+                       const int64_t* out_labels, int n_out, int n_classes, int unknown_id, int64_t* cube, int64_t* open_pred,
+                       int write_idx, void* stream);
+
 /* Few-shot prototype extraction (the recipe at test_embedding.py:413-425 of the reference: mean of features_out over
  * the pixels of one class): sums[c] (device double[C], zeroed by the call) = sum of feats[p][c] over pixels with
  * labels[p] == class_id, count (device uint64) = their number.  C <= 32. */

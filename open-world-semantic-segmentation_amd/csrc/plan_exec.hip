@@ -113,6 +113,7 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_proto_dist_nhwc),
     DML_ENTRY(dml_upsample_nhwc_to_nchw),
     DML_ENTRY(dml_confusion_update),
+    DML_ENTRY(dml_open_set_sweep),
     DML_ENTRY(dml_class_feature_sum),
     DML_ENTRY(dml_class_feature_sums),
     DML_ENTRY(dml_label_encode),

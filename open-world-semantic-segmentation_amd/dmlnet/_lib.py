@@ -18,6 +18,9 @@ STAT_ROWS = 64
 LOSS_BLOCKS = 2048
 FOCAL_PARTIALS = 3 * 2048     # floats of dml_focal_loss_fwd's block_partials
 DISTILL_PARTIALS = 2 * 2048   # floats of dml_distill_fwd's block_partials
+OPEN_SWEEP_SPAN = 2048        # pixels of one workgroup's pass in dml_open_set_sweep
+OPEN_SWEEP_MAX_BLOCKS = 512   # its largest grid: beyond SPAN * MAX_BLOCKS pixels a workgroup makes several passes
+OPEN_SWEEP_MAX_T, OPEN_SWEEP_MAX_CLASSES, OPEN_SWEEP_MAX_OUT = 12, 33, 8
 
 
 def metric_work_doubles(K, C):
@@ -222,6 +225,7 @@ _PROTOS = {
     "dml_fill_f32": (c_i, [c_p, c_i64, c_f, c_p]),
     "dml_convert_dtype": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),
     "dml_confusion_update": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p]),
+    "dml_open_set_sweep": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
     "dml_class_feature_sum": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_p, c_p, c_p]),
     "dml_class_feature_sums": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p]),
     "dml_ood_workspace_bytes": (c_i64, [c_i64]),

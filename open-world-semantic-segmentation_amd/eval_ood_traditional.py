@@ -82,9 +82,13 @@ def confidence(scores, ood, exclude_back=False, feats=None):
     raise NotImplementedError("--ood %s" % ood)
 
 
-def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_back=False):
-    """frames: iterable of (img_resized_list, seg_label int64 [H, W]) on the device."""
+def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_back=False, open_set_thresholds=None):
+    """frames: iterable of (img_resized_list, seg_label int64 [H, W]) on the device.  open_set_thresholds: score the
+    open-set prediction (:537-549, `pred[conf < thre] = out_labels[0]`) at each of them as well (:155-156,599-607) and
+    return the per-threshold results under "open_set"."""
     seg_metrics = metrics_mod.StreamSegMetrics(num_class)
+    sweep = metrics_mod.OpenSetSweepMetrics(num_class, open_set_thresholds, out_labels[0], out_labels) \
+        if open_set_thresholds else None
     aurocs, auprs, fprs, times = [], [], [], []
     known = num_class
     for imgs, seg_label in frames:
@@ -99,13 +103,26 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
         if res is not None:
             aurocs.append(res[0]); auprs.append(res[1]); fprs.append(res[2])
         seg_metrics.update(seg_label[None], pred)
+        if sweep is not None:
+            sweep.update(seg_label, pred, conf)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - tic)
-    return {"auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
-            "aupr": float(np.mean(auprs)) if auprs else float("nan"),
-            "fpr": float(np.mean(fprs)) if fprs else float("nan"),
-            "seg": seg_metrics.get_results(), "sec_per_frame": float(np.mean(times[1:] or times)),
-            "known_iou": known_class_iou(seg_metrics, known)}
+    r = {"auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
+         "aupr": float(np.mean(auprs)) if auprs else float("nan"),
+         "fpr": float(np.mean(fprs)) if fprs else float("nan"),
+         "seg": seg_metrics.get_results(), "sec_per_frame": float(np.mean(times[1:] or times)),
+         "known_iou": known_class_iou(seg_metrics, known)}
+    if sweep is not None:
+        r["open_set"] = sweep.get_results()
+    return r
+
+
+def print_open_set(results):
+    """the per-threshold table and the threshold with the best open-set mean IoU (the reference picks its best threshold
+    the same way, by its unknown IoU, :645-653)"""
+    print(metrics_mod.OpenSetSweepMetrics.to_str(results), end="")
+    best = results[int(np.nanargmax([x["Mean IoU"] for x in results]))]
+    print("Best open-set Mean IoU: %.4f at threshold %.4f" % (best["Mean IoU"], best["Threshold"]))
 
 
 def known_class_iou(seg_metrics, known):
@@ -180,6 +197,10 @@ def build_parser():
     p.add_argument("--crf_iters", type=int, default=CRF["iters"],
                    help="--ood crf-gauss: mean-field steps (the reference's inference(100))")
     p.add_argument("--exclude_back", action="store_true")
+    p.add_argument("--open_set_thresholds", type=float, nargs="+", default=None, metavar="T",
+                   help="also score the open-set prediction (pixels whose confidence is below T become --out_label) at each "
+                        "of these increasing thresholds, at most 12; the reference's sweep is 0.1 ... 0.9 on a confidence "
+                        "normalised to [0, 1]")
     p.add_argument("--out_label", type=int, default=13, help="cfg.OOD.out_labels: the anomaly id of StreetHazards")
     p.add_argument("--num_images", type=int, default=4)
     p.add_argument("--height", type=int, default=720)
@@ -231,10 +252,12 @@ def main():
             lab = coarse.repeat_interleave(32, 0).repeat_interleave(32, 1)[:opts.height, :opts.width].contiguous()
             yield imgs, lab.to(device)
 
-    r = evaluate(seg, frames(), 14, opts.ood, (opts.out_label,), opts.exclude_back)
+    r = evaluate(seg, frames(), 14, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])          # :587-589
     print("Mean IoU: %.4f, Accuracy: %.2f%%, Inference Time: %.4fs" % (r["seg"]["Mean IoU"], 100.0 * r["seg"]["Overall Acc"],
                                                                         r["sec_per_frame"]))
+    if "open_set" in r:
+        print_open_set(r["open_set"])
 
 
 def run_dataset(seg, cfg, opts, num_class, device):
@@ -246,7 +269,7 @@ def run_dataset(seg, cfg, opts, num_class, device):
                                  device=device)
     print("# samples: {}".format(len(reader)))
     tic = time.perf_counter()
-    r = evaluate(seg, reader, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back)
+    r = evaluate(seg, reader, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
     wall = time.perf_counter() - tic
     for i, iou in enumerate(r["known_iou"]):
         print("class [{}], IoU: {:.4f}".format(i, iou))
@@ -256,6 +279,8 @@ def run_dataset(seg, cfg, opts, num_class, device):
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])
     print("Wall clock: {:.2f} frames/s ({} frames, {} decode workers); model only: {:.2f} frames/s"
           .format(len(reader) / wall, len(reader), reader.workers, 1.0 / r["sec_per_frame"]))
+    if "open_set" in r:
+        print_open_set(r["open_set"])
     print("Evaluation Done!")
 
 

@@ -1,5 +1,5 @@
 """Open-world scores computed on the device instead of on 134 MB/img host copies
-(test_embedding.py:339-350,365,428-445; anomaly/eval_ood_traditional.py:301-305,434-448,492-510,511-530)."""
+(test_embedding.py:339-350,365,385-386,428-445; anomaly/eval_ood_traditional.py:301-305,434-448,492-510,511-530,537-549)."""
 from __future__ import annotations
 
 import numpy as np
@@ -127,6 +127,29 @@ def dense_crf_gauss(scores: torch.Tensor, sxy=3.0, compat: float = 3.0, iters: i
                                  held[1].data_ptr(), B, K, H, W, int(first_class), float(sx), float(sy), float(compat),
                                  int(iters), float(clip), _st(scores)), "dml_crf_gauss")
     return (conf, lab) if return_map else conf
+
+
+def open_set_predict(conf: torch.Tensor, preds: torch.Tensor, threshold: float, unknown_id: int) -> torch.Tensor:
+    """The open-set prediction of anomaly/eval_ood_traditional.py:537-549 of the reference (`pred[conf < thre] = 13`;
+    test_embedding.py:385-386 is the same with the sign of its score turned): preds (int64, CUDA) where conf (float32, CUDA,
+    as many elements) >= threshold, `unknown_id` elsewhere -- a NaN confidence is unknown -> int64, shaped like preds.
+    One launch of dml_open_set_sweep with a single threshold and no histogram (unknown_id in 0 .. 32, the library's class
+    range); metrics.OpenSetSweepMetrics scores the same prediction for a list of thresholds without materialising it."""
+    import ctypes
+    _need_cuda(conf)
+    _need_cuda(preds)
+    if conf.dtype != torch.float32 or preds.dtype != torch.int64:
+        raise TypeError("conf must be float32 and preds int64, not %s / %s" % (conf.dtype, preds.dtype))
+    if conf.numel() != preds.numel():
+        raise ValueError("conf and preds differ in size")
+    lib = _lib.load()
+    conf, preds = conf.contiguous(), preds.contiguous()
+    out = torch.empty_like(preds)
+    t = (ctypes.c_float * 1)(float(threshold))
+    _lib.check(lib.dml_open_set_sweep(conf.data_ptr(), preds.data_ptr(), None, preds.numel(), t, 1, None, 0,
+                                      max(2, int(unknown_id) + 1), int(unknown_id), None, out.data_ptr(), 0, _st(conf)),
+               "dml_open_set_sweep")
+    return out
 
 
 def _nhwc_pitch(t):
