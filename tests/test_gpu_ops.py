@@ -876,7 +876,8 @@ def test_sgd_matches_torch(lib):
 @pytest.mark.parametrize("M,N", [(1000, 16), (70001, 16), (5003, 12)])
 def test_bias_grad(lib, M, N):
     """atomics form and the workspace form (per-workgroup partials + fixed-order fold: bitwise reproducible); vector and scalar
-    kernels (N = 12 is not a multiple of the 16-byte vector)"""
+    kernels (N = 12 is three 16-byte vectors of float32 -- the vector kernel -- and no multiple of the eight bfloat16 of one -- the
+    scalar kernel); the edges of both: tests/test_gpu_layout_edges.py"""
     dy = rnd("bg%d" % M, (M, N))
     for dt, tdt in ((0, torch.float32), (1, torch.bfloat16)):
         d = dy.to("cuda", tdt)

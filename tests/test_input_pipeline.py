@@ -96,9 +96,10 @@ def test_device_pipeline_matches_reference_fixture(path):
 
 @pytest.mark.gpu
 def test_device_pipeline_batch_vs_oracle_edge_factors():
-    """batch of frames, explicit parameters: factors exactly 0 / 1 / at the range ends, 0..3 ops, ragged last segment"""
+    """batch of frames, explicit parameters: factors exactly 0 / 1 / at the range ends, 0..3 ops, a ragged segment"""
     rs = np.random.RandomState(5)
-    B, Hh, Ww, crop = 6, 70, 300, (37, 261)          # 261 = 256 + 5: two segments per row
+    B, Hh, Ww, crop = 6, 70, 300, (37, 261)          # 261 = 4 * 65 + 1: ONE segment of 1024 per row, its last thread ragged
+                                                     # (several segments per row: tests/test_gpu_augment_edges.py)
     img = (rs.rand(B, Hh, Ww, 3) * 256).astype(np.uint8)
     img[1] = (img[1] * 0.2).astype(np.uint8)
     img[2] = 255 - (img[2] * 0.1).astype(np.uint8)
