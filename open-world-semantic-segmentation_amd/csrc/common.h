@@ -108,6 +108,114 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) { return wave_sum_d(v); }
+
+// Sum of Q per-lane values over the four waves of a 256-thread workgroup, always in the order ((w0 + w1) + w2) + w3: thread q < Q
+// gets value q as deliver(q, sum).  T needs operator+ and a wave_sum.  The helper owns a __shared__ array: two uses in one kernel
+// need a __syncthreads() between them.
+template <int Q, typename T, typename F> __device__ __forceinline__ void block_fold(const T (&v)[Q], F&& deliver) {
+    __shared__ T sh[4][Q];
+    T w[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) w[q] = wave_sum(v[q]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) sh[threadIdx.x >> 6][q] = w[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < Q) {
+        const int q = threadIdx.x;
+        deliver(q, ((sh[0][q] + sh[1][q]) + sh[2][q]) + sh[3][q]);
+    }
+}
+
+// ---- the pixel kernels' shared pieces
+constexpr int MAXC = 32, MAXK = 33;   // channels or classes a lane keeps in registers / prototype rows of the distance head
+constexpr int MAX_BLOCKS = 2048;      // workgroups of a launch that leaves one partial each: what the callers' buffers hold
+// non-temporal stores of logits / features: standalone head 0.378 -> 0.358 ms, staged x4 kernel 0.237 -> 0.219 ms
+// (tools/bench_dist_variants.py, 768 x 768 x 16)
+constexpr bool DIST_NT_DEFAULT = true;
+
+// 16-byte load / store; NT = true marks it non-temporal: a stream that is read once or that nobody re-reads from cache (logits and
+// features, 1.2 GB per step, far beyond L2)
+template <bool NT = false> __device__ __forceinline__ float4 load4(const float* p) {
+    if constexpr (NT) {
+        typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+        const f32x4_nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
+        return make_float4(t.x, t.y, t.z, t.w);
+    } else {
+        return *reinterpret_cast<const float4*>(p);
+    }
+}
+template <bool NT = false> __device__ __forceinline__ void store4(float* p, const float4 v) {
+    if constexpr (NT) {
+        typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+        f32x4_nt t = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(t, reinterpret_cast<f32x4_nt*>(p));
+    } else {
+        *reinterpret_cast<float4*>(p) = v;
+    }
+}
+// PX = 1 or 4 consecutive floats of one lane: 16 bytes when PX == 4
+template <int PX, bool NT = false> __device__ __forceinline__ void load_px(const float* p, float (&v)[PX]) {
+    if constexpr (PX == 4) {
+        const float4 t = load4<NT>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+template <int PX, bool NT = false> __device__ __forceinline__ void store_px(float* p, const float (&v)[PX]) {
+    if constexpr (PX == 4) store4<NT>(p, make_float4(v[0], v[1], v[2], v[3]));
+    else *p = v[0];
+}
+// four floats of which only the first `left` are there: VEC (left >= 4 and p 16-byte aligned) takes them as one vector
+template <bool VEC> __device__ __forceinline__ void load4_tail(const float* p, uint32_t left, float (&v)[4]) {
+    if constexpr (VEC) {
+        Vec16<float>::load(p, v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (uint32_t)k < left ? p[k] : 0.f;
+    }
+}
+template <bool VEC> __device__ __forceinline__ void store4_tail(float* p, uint32_t left, const float (&v)[4]) {
+    if constexpr (VEC) {
+        Vec16<float>::store(p, v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((uint32_t)k < left) p[k] = v[k];
+    }
+}
+
+// Bilinear resize, align_corners = False (PyTorch's area_pixel_compute_source_index): the two source taps of output index I on an
+// axis of n samples at scale s = n / N.  Every kernel that resizes goes through this, so they all see the same coordinates and
+// weights:  src = max(s * (I + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < n - 1), l1 = src - i0
+struct Tap {
+    int i0, i1;        // clamped neighbours (i1 == i0 on the last sample)
+    float l0, l1;      // their weights
+};
+__device__ __forceinline__ Tap src_tap(float s, int I, int n) {
+    float sI = s * ((float)I + 0.5f) - 0.5f;
+    sI = sI < 0.f ? 0.f : sI;
+    Tap t;
+    t.i0 = min((int)sI, n - 1);
+    t.i1 = t.i0 + (t.i0 < n - 1 ? 1 : 0);
+    t.l1 = sI - (float)t.i0;
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+
+__device__ __forceinline__ void load_protos(float* sp, const float* __restrict__ protos, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) sp[i] = protos[i];
+    __syncthreads();
+}
+
+// every pointer is a multiple of `bytes` (a power of two); a null pointer counts as aligned
+template <typename... P> static inline bool aligned_to(uintptr_t bytes, const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & (bytes - 1)) == 0;
+}
+template <typename... P> static inline bool aligned16(const P*... p) { return aligned_to(16, p...); }
 
 // Workgroups for a grid-stride streaming kernel.  Caps of 2048 and above are "enough to fill the chip" choices, not
 // buffer sizes (short-lived workgroups stream faster than persistent ones, see bn.hip).

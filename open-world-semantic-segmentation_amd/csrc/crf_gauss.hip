@@ -22,7 +22,6 @@
 
 namespace {
 
-constexpr int CRF_MAXC = 32;        // head.hip's MAXC: a pixel's messages stay in registers
 constexpr int CRF_MAXR = 48;        // ceil(6 sigma), sigma <= 8
 constexpr int CRF_TAB = 128;        // floats of one tap table
 // tap tables, zero outside |d| <= R: wx[i] = kx(i - Rpx - CRF_XPAD) (Rpx = Rx rounded up to 4; read up to i = 2 Rpx + 7 <= 103),
@@ -105,24 +104,24 @@ __global__ __launch_bounds__(256) void crf_init_kernel(const float* __restrict__
     const int64_t obase = (int64_t)b * C * HW;
     for (int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pix < HW;
          pix += (int64_t)(gridDim.x - 1) * blockDim.x) {
-        float a[CRF_MAXC];
+        float a[MAXC];
 #pragma unroll
-        for (int c = 0; c < CRF_MAXC; ++c)
+        for (int c = 0; c < MAXC; ++c)
             if (c < C) a[c] = img[(int64_t)c * HW + pix];
-        crf_softmax<CRF_MAXC>(a, C);
+        crf_softmax<MAXC>(a, C);
 #pragma unroll
-        for (int c = 0; c < CRF_MAXC; ++c)
+        for (int c = 0; c < MAXC; ++c)
             if (c < C) {
                 const float u = -logf(fminf(fmaxf(a[c], clip), 1.f));
                 U[obase + (int64_t)c * HW + pix] = u;
                 a[c] = -u;
             }
-        crf_softmax<CRF_MAXC>(a, C);
+        crf_softmax<MAXC>(a, C);
         if (last) {
-            crf_write_result<CRF_MAXC>(a, C, conf, map, (int64_t)b * HW + pix);
+            crf_write_result<MAXC>(a, C, conf, map, (int64_t)b * HW + pix);
         } else {
 #pragma unroll
-            for (int c = 0; c < CRF_MAXC; ++c)
+            for (int c = 0; c < MAXC; ++c)
                 if (c < C) Q[obase + (int64_t)c * HW + pix] = a[c];
         }
     }
@@ -321,7 +320,7 @@ void crf_col_launch(const float* T, const float* U, float* Q, float* conf, int64
 // the checks the two entry points share; 0 = a supported call
 int crf_check_shape(int B, int C, int H, int W) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return DML_EINVAL;
-    if (C > CRF_MAXC || B > 65535) return DML_EUNSUPPORTED;
+    if (C > MAXC || B > 65535) return DML_EUNSUPPORTED;
     // the image index is the grid's y; 2^40 pixels keep every offset (x 32 channels x 3 tensors x 4 bytes) inside int64
     if ((int64_t)H * W > (1ll << 40) / B) return DML_EUNSUPPORTED;
     return 0;
@@ -354,7 +353,7 @@ extern "C" int dml_crf_gauss(const float* logits, float* conf, int64_t* map, voi
     hipLaunchKernelGGL(crf_init_kernel, dim3(grid_for(HW, 256, 2048) + 1, B), dim3(256), 0, st, logits, U, Q, conf, map, tabs, K,
                        k_first, H, W, inv2sx2, inv2sy2, Rx, Ry, clip, iters == 0 ? 1 : 0);
     // with W % 4 == 0 every row of Q and T and the nx table keep the workspace's alignment
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(work) & 15) == 0;
+    const bool vec = W % 4 == 0 && aligned16(work);
     const int Rpx = crf_rp(Rx);
     const int row_tiles_x = (W + CRF_ROW_TX - 1) / CRF_ROW_TX;
     const int64_t rows = (int64_t)B * C * H;

@@ -17,29 +17,7 @@
 
 namespace {
 
-constexpr int DISTILL_BLOCKS = 2048;      // most workgroups of the forward; block_partials holds 2 floats for each
-constexpr int DISTILL_MAXC = 32;
-
 typedef float distill_f4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at any 4-byte boundary
-
-template <bool VEC> __device__ __forceinline__ void distill_load(const float* p, uint32_t left, float (&v)[4]) {
-    if constexpr (VEC) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (uint32_t)k < left ? p[k] : 0.f;
-    }
-}
-template <bool VEC> __device__ __forceinline__ void distill_store(float* p, uint32_t left, const float (&v)[4]) {
-    if constexpr (VEC) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if ((uint32_t)k < left) p[k] = v[k];
-    }
-}
 
 // the four teacher floats from tb on, zero past the image's end (nT floats)
 __device__ __forceinline__ void distill_load_teacher(const float* timg, uint32_t tb, uint32_t nT, float (&tv)[4]) {
@@ -54,14 +32,14 @@ __device__ __forceinline__ void distill_load_teacher(const float* timg, uint32_t
 
 // first maximal class of a pixel's teacher logits (NCHW; the tie rule of dml_argmax_msp); every load is issued before the first use
 __device__ __forceinline__ int64_t distill_argmax(const float* lg, int Ct, int64_t HW) {
-    float v[DISTILL_MAXC];
+    float v[MAXC];
 #pragma unroll
-    for (int k = 0; k < DISTILL_MAXC; ++k)
+    for (int k = 0; k < MAXC; ++k)
         if (k < Ct) v[k] = lg[(int64_t)k * HW];
     float best = v[0];
     int bi = 0;
 #pragma unroll
-    for (int k = 1; k < DISTILL_MAXC; ++k)
+    for (int k = 1; k < MAXC; ++k)
         if (k < Ct && v[k] > best) { best = v[k]; bi = k; }
     return bi;
 }
@@ -77,7 +55,7 @@ __device__ __forceinline__ void distill_group(const float* timg, const float* si
     uint32_t pix = fdiv(e0, divCs);
     int c = (int)(e0 - pix * (uint32_t)Cs);
     float sv[4], tv[4];
-    distill_load<VEC>(simg + e0, left, sv);
+    load4_tail<VEC>(simg + e0, left, sv);
     distill_load_teacher(timg, pix * (uint32_t)Ct + (uint32_t)(c < Ct ? c : Ct), nT, tv);
     int j = 0;
     bool in = false;
@@ -107,19 +85,27 @@ __device__ __forceinline__ void distill_accumulate(const float (&d)[4], const bo
     }
 }
 
-// a workgroup's partial = (sum d^2, #pixels as the bits of a uint32: exact whatever the workgroup's share of the image is)
-__device__ __forceinline__ void distill_block_partial(float acc, uint32_t cnt, float* out) {
-    __shared__ float sh[4];
-    __shared__ uint32_t shc[4];
-    acc = wave_sum(acc);
+// a workgroup's partial = (sum d^2, #pixels as the bits of a uint32: exact whatever the workgroup's share of the image is), folded as
+// one value of common.h's block_fold: the float by wave_sum, the count by integer additions
+struct DistillPartial {
+    float acc;
+    uint32_t cnt;
+};
+__device__ __forceinline__ DistillPartial operator+(const DistillPartial& a, const DistillPartial& b) {
+    return {a.acc + b.acc, a.cnt + b.cnt};
+}
+__device__ __forceinline__ DistillPartial wave_sum(DistillPartial v) {
+    v.acc = ::wave_sum(v.acc);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = acc; shc[threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = sh[0] + sh[1] + sh[2] + sh[3];
-        out[1] = __uint_as_float(shc[0] + shc[1] + shc[2] + shc[3]);
-    }
+    for (int o = 32; o > 0; o >>= 1) v.cnt += (uint32_t)__shfl_xor((int)v.cnt, o, 64);
+    return v;
+}
+__device__ __forceinline__ void distill_block_partial(float acc, uint32_t cnt, float* out) {
+    const DistillPartial v[1] = {{acc, cnt}};
+    block_fold(v, [&](int, const DistillPartial& s) {
+        out[0] = s.acc;
+        out[1] = __uint_as_float(s.cnt);
+    });
 }
 
 // Without teacher logits.  grid (bpi, B): workgroup (j, b) takes the groups j * 256 + lane, stepping bpi * 256, of image b; a lane
@@ -193,7 +179,7 @@ __global__ __launch_bounds__(256) void distill_fwd_fill_kernel(const float* __re
 
 // the double fold of the workgroups' partials in a fixed order: a wave per image, then one wave over the images' S / cnt
 __global__ __launch_bounds__(256) void distill_sum_kernel(const float* __restrict__ partials, int B, int bpi, double* sums) {
-    __shared__ double ratio[DISTILL_BLOCKS];
+    __shared__ double ratio[MAX_BLOCKS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int i = wv; i < B; i += 4) {
         double a = 0, c = 0;
@@ -246,21 +232,21 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restric
                            first);
 #pragma unroll
         for (int k = 0; k < 4; ++k) r[k] = m[k] ? w * d[k] : 0.f;
-        distill_store<VEC>(gimg + 4u * (uint32_t)g, n_img - 4u * (uint32_t)g, r);
+        store4_tail<VEC>(gimg + 4u * (uint32_t)g, n_img - 4u * (uint32_t)g, r);
     }
 }
 
 int distill_shape_check(int B, int Ct, int Cs, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0 || Ct < 1 || Ct > Cs || Cs > DISTILL_MAXC) return DML_EINVAL;
-    if (B > DISTILL_BLOCKS || (int64_t)H * W * Cs >= ((int64_t)1 << 31)) return DML_EUNSUPPORTED;
+    if (B <= 0 || H <= 0 || W <= 0 || Ct < 1 || Ct > Cs || Cs > MAXC) return DML_EINVAL;
+    if (B > MAX_BLOCKS || (int64_t)H * W * Cs >= ((int64_t)1 << 31)) return DML_EUNSUPPORTED;
     return 0;
 }
 int distill_bpi(int B, int64_t HW, int Cs) {
     const int64_t groups = (HW * Cs + 3) / 4;
-    return grid_for(groups, 256, DISTILL_BLOCKS / B);
+    return grid_for(groups, 256, MAX_BLOCKS / B);
 }
 bool distill_vec(int64_t HW, int Cs, const void* a, const void* b) {
-    return (HW * Cs) % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
+    return (HW * Cs) % 4 == 0 && aligned16(a, b);
 }
 
 }  // namespace
@@ -272,7 +258,7 @@ extern "C" int dml_distill_fwd(const float* t_logits, const float* t, const floa
     if (const int rc = distill_shape_check(B, Ct, Cs, H, W)) return rc;
     const int64_t HW = (int64_t)H * W;
     const bool vec = distill_vec(HW, Cs, s, nullptr), fill = t_logits != nullptr;
-    const int bpi = fill ? grid_for((HW + 255) / 256, 1, DISTILL_BLOCKS / B) : distill_bpi(B, HW, Cs);      // tiles : groups
+    const int bpi = fill ? grid_for((HW + 255) / 256, 1, MAX_BLOCKS / B) : distill_bpi(B, HW, Cs);      // tiles : groups
     const FastDiv divCs = make_fastdiv((uint32_t)Cs);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define DISTILL_FILL(VEC)                                                                                                      \

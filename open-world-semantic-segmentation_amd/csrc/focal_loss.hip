@@ -7,22 +7,9 @@
 namespace {
 
 constexpr int FOCAL_KREG = 16;        // up to this many classes a pixel's logits are loaded up front and, in the backward, kept
-constexpr int FOCAL_BLOCKS = 2048;    // most workgroups of either pass; block_partials holds 3 floats for each
 
 typedef long long focal_ll2 __attribute__((ext_vector_type(2)));
 
-template <int PX> __device__ __forceinline__ void focal_load(const float* p, float (&v)[PX]) {
-    if constexpr (PX == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-template <int PX> __device__ __forceinline__ void focal_store(float* p, const float (&v)[PX]) {
-    if constexpr (PX == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
 template <int PX> __device__ __forceinline__ void focal_load_labels(const int64_t* p, int64_t (&lab)[PX]) {
     if constexpr (PX == 4) {
         const focal_ll2 a = reinterpret_cast<const focal_ll2*>(p)[0], b = reinterpret_cast<const focal_ll2*>(p)[1];
@@ -71,7 +58,6 @@ template <int PX, bool REG>
 __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                         float* __restrict__ partials, int B, int K, int64_t HW,
                                                         int64_t ignore_index, float alpha, float gamma) {
-    __shared__ float sh[4][3];
     float s_fl = 0.f, s_cnt = 0.f, s_ok = 0.f;
     const int64_t gpi = HW / PX, total = (int64_t)B * gpi;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -95,14 +81,14 @@ __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict_
             float reg[FOCAL_KREG][PX];
 #pragma unroll
             for (int k = 0; k < FOCAL_KREG; ++k)
-                if (k < K) focal_load<PX>(src + (int64_t)k * HW, reg[k]);
+                if (k < K) load_px<PX>(src + (int64_t)k * HW, reg[k]);
 #pragma unroll
             for (int k = 0; k < FOCAL_KREG; ++k)
                 if (k < K) step(reg[k], k);
         } else {
             for (int k = 0; k < K; ++k) {
                 float v[PX];
-                focal_load<PX>(src + (int64_t)k * HW, v);
+                load_px<PX>(src + (int64_t)k * HW, v);
                 step(v, k);
             }
         }
@@ -114,36 +100,18 @@ __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict_
             s_ok += (bi[p] == (int)lab[p]) ? 1.f : 0.f;
         }
     }
-    s_fl = wave_sum(s_fl); s_cnt = wave_sum(s_cnt); s_ok = wave_sum(s_ok);
-    if ((threadIdx.x & 63) == 0) {
-        const int wv = threadIdx.x >> 6;
-        sh[wv][0] = s_fl; sh[wv][1] = s_cnt; sh[wv][2] = s_ok;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int q = threadIdx.x;
-        partials[(int64_t)blockIdx.x * 3 + q] = sh[0][q] + sh[1][q] + sh[2][q] + sh[3][q];
-    }
+    const float s[3] = {s_fl, s_cnt, s_ok};
+    block_fold(s, [&](int q, float v) { partials[(int64_t)blockIdx.x * 3 + q] = v; });
 }
 
 // the double fold of the workgroups' partials, in a fixed order; sums = { sum fl, #valid, #pixels, #correct }
 __global__ __launch_bounds__(256) void focal_sum_kernel(const float* __restrict__ partials, int nblocks, double* sums,
                                                         double pixels) {
-    __shared__ double sh[4][3];
     double acc[3] = {0, 0, 0};
     for (int i = threadIdx.x; i < nblocks; i += blockDim.x)
 #pragma unroll
         for (int q = 0; q < 3; ++q) acc[q] += (double)partials[(int64_t)i * 3 + q];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[q] = wave_sum_d(acc[q]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) sh[threadIdx.x >> 6][q] = acc[q];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int q = threadIdx.x;
-        sums[q == 2 ? 3 : q] = sh[0][q] + sh[1][q] + sh[2][q] + sh[3][q];
-    }
+    block_fold(acc, [&](int q, double v) { sums[q == 2 ? 3 : q] = v; });
     if (threadIdx.x == 3) sums[2] = pixels;
 }
 
@@ -175,7 +143,7 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
         if constexpr (REG) {
 #pragma unroll
             for (int k = 0; k < FOCAL_KREG; ++k)
-                if (k < K) focal_load<PX>(src + (int64_t)k * HW, reg[k]);
+                if (k < K) load_px<PX>(src + (int64_t)k * HW, reg[k]);
 #pragma unroll
             for (int k = 0; k < FOCAL_KREG; ++k)
                 if (k < K) {
@@ -188,7 +156,7 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
         } else {
             for (int k = 0; k < K; ++k) {
                 float v[PX];
-                focal_load<PX>(src + (int64_t)k * HW, v);
+                load_px<PX>(src + (int64_t)k * HW, v);
 #pragma unroll
                 for (int p = 0; p < PX; ++p) {
                     focal_lse_step(v[p], mx[p], rest[p]);
@@ -211,7 +179,7 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
                 if ((int64_t)k == lab[p]) g[p] -= wm[p];
                 if (lab[p] == ignore_index) g[p] = 0.f;
             }
-            focal_store<PX>(dst + (int64_t)k * HW, g);
+            store_px<PX>(dst + (int64_t)k * HW, g);
         };
         if constexpr (REG) {
 #pragma unroll
@@ -220,16 +188,13 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
         } else {
             for (int k = 0; k < K; ++k) {
                 float v[PX];
-                focal_load<PX>(src + (int64_t)k * HW, v);                       // cache-resident re-read
+                load_px<PX>(src + (int64_t)k * HW, v);                       // cache-resident re-read
                 grad(v, k);
             }
         }
     }
 }
 
-bool focal_aligned16(const void* a, const void* b, const void* c) {
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
-}
 bool focal_params_ok(float alpha, float gamma) { return isfinite(alpha) && isfinite(gamma) && gamma >= 0.f; }
 
 }  // namespace
@@ -239,8 +204,8 @@ extern "C" int dml_focal_loss_fwd(const float* logits, const int64_t* labels, do
     if (!logits || !labels || !sums || !block_partials || B <= 0 || K < 1 || H <= 0 || W <= 0 || !focal_params_ok(alpha, gamma))
         return DML_EINVAL;
     const int64_t HW = (int64_t)H * W;
-    const bool v4 = (HW % 4) == 0 && focal_aligned16(logits, labels, nullptr);
-    const int grid = grid_for(B * HW / (v4 ? 4 : 1), 256, FOCAL_BLOCKS);
+    const bool v4 = (HW % 4) == 0 && aligned16(logits, labels);
+    const int grid = grid_for(B * HW / (v4 ? 4 : 1), 256, MAX_BLOCKS);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool reg = K <= FOCAL_KREG;
 #define FOCAL_FWD(PX, REG)                                                                                              \
@@ -270,9 +235,9 @@ extern "C" int dml_focal_loss_bwd(const float* logits, const int64_t* labels, co
     if (!logits || !labels || !sums || !glogits || B <= 0 || K < 1 || H <= 0 || W <= 0 || !focal_params_ok(alpha, gamma))
         return DML_EINVAL;
     const int64_t HW = (int64_t)H * W;
-    const bool v4 = (HW % 4) == 0 && focal_aligned16(logits, labels, glogits);
+    const bool v4 = (HW % 4) == 0 && aligned16(logits, labels, glogits);
     const bool reg = K <= FOCAL_KREG;
-    const int grid = grid_for(B * HW / (v4 ? 4 : 1), 256, FOCAL_BLOCKS);
+    const int grid = grid_for(B * HW / (v4 ? 4 : 1), 256, MAX_BLOCKS);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define FOCAL_BWD(PX, REG)                                                                                              \
     hipLaunchKernelGGL((focal_bwd_kernel<PX, REG>), dim3(grid), dim3(256), 0, st, logits, labels, sums, gout, glogits, B, K, \

@@ -14,7 +14,6 @@ namespace {
 
 constexpr int KNN_TY = 16, KNN_TX = 64, KNN_THREADS = 256;
 constexpr int KNN_MAXR = 16;       // neighbor_size <= 17
-constexpr int KNN_MAXC = 32;       // head.hip's MAXC
 constexpr int KNN_MAX_GRID = 16384;
 
 __host__ __device__ constexpr int knn_rp(int R) { return (R + 3) & ~3; }   // halo columns kept left and right: R rounded up to whole 16-byte vectors
@@ -187,19 +186,18 @@ void knn_launch(const float* feats, float* score, int B, int C, int H, int W, in
                        (int)tiles);
 }
 
-bool knn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
 extern "C" int dml_knn_cosine_score(const float* feats, float* score, int B, int C, int H, int W, int neighbor_size,
                                     void* stream) {
     if (!feats || !score || B <= 0 || C <= 0 || H <= 0 || W <= 0 || neighbor_size < 1) return DML_EINVAL;
-    if (C > KNN_MAXC || neighbor_size > KNN_MAXR + 1 || B > 65535) return DML_EUNSUPPORTED;
+    if (C > MAXC || neighbor_size > KNN_MAXR + 1 || B > 65535) return DML_EUNSUPPORTED;
     // the image index is the grid's y; 2^40 pixels keep every element offset (x C, x 4 bytes) inside int64
     if ((int64_t)H * W > (1ll << 40) / B) return DML_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int R = neighbor_size - 1;
-    const bool vec = W % 4 == 0 && knn_aligned16(feats) && knn_aligned16(score);
+    const bool vec = W % 4 == 0 && aligned16(feats, score);
     if (R == 8 && vec) knn_launch<8, true>(feats, score, B, C, H, W, R, st);
     else if (R == 8) knn_launch<8, false>(feats, score, B, C, H, W, R, st);
     else if (vec) knn_launch<0, true>(feats, score, B, C, H, W, R, st);

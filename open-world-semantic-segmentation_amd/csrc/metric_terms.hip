@@ -27,30 +27,10 @@
 
 namespace {
 
-constexpr int METRIC_BLOCKS = 2048;      // most workgroups of a forward launch; work holds 2 + K (C + 1) doubles for each
-constexpr int METRIC_MAX = 32;           // classes and channels at most
+// MAX_BLOCKS: most workgroups of a forward launch; work holds 2 + K (C + 1) doubles for each.  MAXC: classes and channels at most.
 
 __device__ __forceinline__ bool metric_valid(int64_t lab, int64_t ignore_index, int K) {
     return lab != ignore_index && (uint64_t)lab < (uint64_t)K;      // never an index outside a [K] table
-}
-
-template <bool VEC> __device__ __forceinline__ void metric_load(const float* p, uint32_t left, float (&v)[4]) {
-    if constexpr (VEC) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (uint32_t)k < left ? p[k] : 0.f;
-    }
-}
-template <bool VEC> __device__ __forceinline__ void metric_store(float* p, uint32_t left, const float (&v)[4]) {
-    if constexpr (VEC) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if ((uint32_t)k < left) p[k] = v[k];
-    }
 }
 
 // ---- per workgroup: sum of the features and number of pixels of every class
@@ -139,7 +119,7 @@ __device__ __forceinline__ void metric_group(const float* fimg, const int64_t* l
     uint32_t pix = fdiv(e0, divC);
     int c = (int)(e0 - pix * (uint32_t)C);
     float v[4];
-    metric_load<VEC>(fimg + e0, left, v);
+    load4_tail<VEC>(fimg + e0, left, v);
     int row = 0;
     bool in = false;
 #pragma unroll
@@ -163,8 +143,7 @@ __global__ __launch_bounds__(256) void metric_terms_kernel(const float* __restri
                                                            double* __restrict__ partials, int K, int C, int64_t HW, FastDiv divC,
                                                            int64_t ignore_index) {
 #pragma clang fp contract(off)
-    __shared__ float mu[METRIC_MAX * METRIC_MAX];
-    __shared__ float sh[4][2];
+    __shared__ float mu[MAXC * MAXC];
     const int64_t b = blockIdx.y;
     const int64_t* limg = labels + b * HW;
     float center = 0.f, inter = 0.f;
@@ -198,7 +177,7 @@ __global__ __launch_bounds__(256) void metric_terms_kernel(const float* __restri
 #pragma unroll 4
             for (int k = 0; k < K; ++k) {
                 float v[4];
-                metric_load<VECL>(limg_l + (int64_t)k * HW + p, left, v);
+                load4_tail<VECL>(limg_l + (int64_t)k * HW + p, left, v);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     if (k != lab[j]) s[j] = s[j] + v[j];
@@ -208,20 +187,14 @@ __global__ __launch_bounds__(256) void metric_terms_kernel(const float* __restri
                 if (lab[j] >= 0) inter = inter + s[j];
         }
     }
-    center = wave_sum(center);
-    inter = wave_sum(inter);
-    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6][0] = center; sh[threadIdx.x >> 6][1] = inter; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const int q = threadIdx.x;
-        partials[((int64_t)b * gridDim.x + blockIdx.x) * 2 + q] = (double)(((sh[0][q] + sh[1][q]) + sh[2][q]) + sh[3][q]);
-    }
+    const float s[2] = {center, inter};
+    block_fold(s, [&](int q, float v) { partials[((int64_t)b * gridDim.x + blockIdx.x) * 2 + q] = (double)v; });
 }
 
 // ---- the double fold of the (centre, inter) partials in a fixed order: a wave per image, then one wave over the images
 __global__ __launch_bounds__(256) void metric_fold_kernel(const double* __restrict__ partials, int B, int bpi, double inv_hw,
                                                           double* __restrict__ sums) {
-    __shared__ double img[2 * METRIC_BLOCKS];
+    __shared__ double img[2 * MAX_BLOCKS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int i = wv; i < B; i += 4) {
         double ce = 0, in = 0;
@@ -260,7 +233,7 @@ __global__ __launch_bounds__(256) void metric_gfeats_kernel(const float* __restr
                                                             int C, int64_t HW, FastDiv divC, int64_t ignore_index, float gamma,
                                                             float n_images) {
 #pragma clang fp contract(off)
-    __shared__ float mu[METRIC_MAX * METRIC_MAX];
+    __shared__ float mu[MAXC * MAXC];
     const int64_t b = blockIdx.y;
     for (int i = threadIdx.x; i < K * C; i += 256) mu[i] = means[b * K * C + i];
     __syncthreads();
@@ -277,7 +250,7 @@ __global__ __launch_bounds__(256) void metric_gfeats_kernel(const float* __restr
         metric_group<VEC>(fimg, limg, mu, (uint32_t)g, n_img, K, C, divC, ignore_index, d, m);
 #pragma unroll
         for (int k = 0; k < 4; ++k) r[k] = m[k] ? w * d[k] : 0.f;
-        metric_store<VEC>(gimg + 4u * (uint32_t)g, n_img - 4u * (uint32_t)g, r);
+        store4_tail<VEC>(gimg + 4u * (uint32_t)g, n_img - 4u * (uint32_t)g, r);
     }
 }
 
@@ -305,18 +278,18 @@ __global__ __launch_bounds__(256) void metric_glogits_kernel(const int64_t* __re
 #pragma unroll 4
         for (int k = 0; k < K; ++k) {
             float v[4];
-            metric_load<VEC>(gimg + (int64_t)k * HW + p, left, v);
+            load4_tail<VEC>(gimg + (int64_t)k * HW + p, left, v);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (lab[j] >= 0 && lab[j] != k) v[j] = v[j] + w;
-            metric_store<VEC>(gimg + (int64_t)k * HW + p, left, v);
+            store4_tail<VEC>(gimg + (int64_t)k * HW + p, left, v);
         }
     }
 }
 
 int metric_shape_check(int B, int K, int C, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || K < 1 || C < 1) return DML_EINVAL;
-    if (K > METRIC_MAX || C > METRIC_MAX || B > METRIC_BLOCKS || (int64_t)H * W * C >= ((int64_t)1 << 31)) return DML_EUNSUPPORTED;
+    if (K > MAXC || C > MAXC || B > MAX_BLOCKS || (int64_t)H * W * C >= ((int64_t)1 << 31)) return DML_EUNSUPPORTED;
     return 0;
 }
 int metric_cp(int C) {
@@ -324,10 +297,10 @@ int metric_cp(int C) {
     while (cp < C) cp *= 2;
     return cp;
 }
-int metric_bpi_sums(int B, int64_t HW, int C) { return grid_for(HW, 4 * (64 / metric_cp(C)), METRIC_BLOCKS / B); }
-int metric_bpi_flat(int B, int64_t HW, int C) { return grid_for((HW * C + 3) / 4, 256, METRIC_BLOCKS / B); }
-int metric_bpi_quads(int B, int64_t HW) { return grid_for((HW + 3) / 4, 256, METRIC_BLOCKS / B); }
-bool metric_vec(int64_t n_img, const void* a, const void* b) { return n_img % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0; }
+int metric_bpi_sums(int B, int64_t HW, int C) { return grid_for(HW, 4 * (64 / metric_cp(C)), MAX_BLOCKS / B); }
+int metric_bpi_flat(int B, int64_t HW, int C) { return grid_for((HW * C + 3) / 4, 256, MAX_BLOCKS / B); }
+int metric_bpi_quads(int B, int64_t HW) { return grid_for((HW + 3) / 4, 256, MAX_BLOCKS / B); }
+bool metric_vec(int64_t n_img, const void* a, const void* b) { return n_img % 4 == 0 && aligned16(a, b); }
 
 }  // namespace
 
@@ -338,7 +311,7 @@ extern "C" int dml_metric_fwd(const float* logits, const float* feats, const int
     const int64_t HW = (int64_t)H * W;
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* term_partials = work;
-    double* class_partials = work + 2 * METRIC_BLOCKS;
+    double* class_partials = work + 2 * MAX_BLOCKS;
     if (feats) {
         const int bpi = metric_bpi_sums(B, HW, C), cp = metric_cp(C);
         const size_t lds = (size_t)4 * K * (64 + 64 / cp) * sizeof(float);

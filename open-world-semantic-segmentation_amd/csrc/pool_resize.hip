@@ -129,23 +129,7 @@ __global__ __launch_bounds__(256) void broadcast_hw_kernel(const T* __restrict__
 }
 
 // ------------------------------------------------------------------------------- bilinear resize
-// PyTorch area_pixel_compute_source_index, align_corners = False:
-//   src = max(scale * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), lambda = src - i0
-struct Lerp {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ Lerp src_index(int dst, float scale, int in) {
-    float s = scale * ((float)dst + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    Lerp r;
-    r.i0 = min((int)s, in - 1);
-    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-    r.l1 = s - (float)r.i0;
-    r.l0 = 1.f - r.l1;
-    return r;
-}
-
+// (the source taps: common.h's src_tap)
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const TI* __restrict__ x, TO* __restrict__ y, int B,
                                                            int h, int w, int H, int W, int C, int ldx, int ldy,
@@ -160,7 +144,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const TI* __restrict_
         const int X = (int)(p % W); p /= W;
         const int Y = (int)(p % H);
         const int b = (int)(p / H);
-        const Lerp ly = src_index(Y, sy, h), lx = src_index(X, sx, w);
+        const Tap ly = src_tap(sy, Y, h), lx = src_tap(sx, X, w);
         const TI* base = x + (int64_t)b * h * w * ldx + cv * V;
         float o[V];
 #pragma unroll
@@ -192,7 +176,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_planes_kernel(const float* _
         const int X = (int)(p % W); p /= W;
         const int Y = (int)(p % H);
         const int b = (int)(p / H);
-        const Lerp ly = src_index(Y, sy, h), lx = src_index(X, sx, w);
+        const Tap ly = src_tap(sy, Y, h), lx = src_tap(sx, X, w);
         const float* base = x + (int64_t)b * h * w * ldx + cv * 4;
         const float4 v00 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i0 * w + lx.i0) * ldx);
         const float4 v01 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i0 * w + lx.i1) * ldx);
@@ -238,11 +222,11 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const TI* __restrict_
         const int X1 = min(W - 1, (int)ceilf(((float)xs + 1.5f) / sx - 0.5f) + 1);
         float acc[V] = {0.f, 0.f, 0.f, 0.f};
         for (int Y = Y0; Y <= Y1; ++Y) {
-            const Lerp ly = src_index(Y, sy, h);
+            const Tap ly = src_tap(sy, Y, h);
             const float wy = (ly.i0 == ys ? ly.l0 : 0.f) + (ly.i1 == ys ? ly.l1 : 0.f);
             if (wy == 0.f) continue;
             for (int X = X0; X <= X1; ++X) {
-                const Lerp lx = src_index(X, sx, w);
+                const Tap lx = src_tap(sx, X, w);
                 const float wx = (lx.i0 == xs ? lx.l0 : 0.f) + (lx.i1 == xs ? lx.l1 : 0.f);
                 if (wx == 0.f) continue;
                 const TI* g = dy + (((int64_t)b * H + Y) * W + X) * lddy + cv * V;
@@ -269,7 +253,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_bf16v_kernel(const bf16_t* _
     const int X = (int)(p % W); p /= W;
     const int Y = (int)(p % H);
     const int b = (int)(p / H);
-    const Lerp ly = src_index(Y, sy, h), lx = src_index(X, sx, w);
+    const Tap ly = src_tap(sy, Y, h), lx = src_tap(sx, X, w);
     const bf16_t* base = x + (int64_t)b * h * w * ldx + cv * 8;
     float v00[8], v01[8], v10[8], v11[8], o[8];
     Vec16<bf16_t>::load(base + ((int64_t)ly.i0 * w + lx.i0) * ldx, v00);
@@ -299,11 +283,11 @@ __global__ __launch_bounds__(256) void bilinear_bwd_bf16v_kernel(const bf16_t* _
     const int X1 = min(W - 1, (int)ceilf(((float)xs + 1.5f) / sx - 0.5f) + 1);
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int Y = Y0; Y <= Y1; ++Y) {
-        const Lerp ly = src_index(Y, sy, h);
+        const Tap ly = src_tap(sy, Y, h);
         const float wy = (ly.i0 == ys ? ly.l0 : 0.f) + (ly.i1 == ys ? ly.l1 : 0.f);
         if (wy == 0.f) continue;
         for (int X = X0; X <= X1; ++X) {
-            const Lerp lx = src_index(X, sx, w);
+            const Tap lx = src_tap(sx, X, w);
             const float wx = (lx.i0 == xs ? lx.l0 : 0.f) + (lx.i1 == xs ? lx.l1 : 0.f);
             if (wx == 0.f) continue;
             float g[8];
@@ -643,14 +627,14 @@ __global__ __launch_bounds__(256) void upsample_to_nchw_kernel(const float* __re
         const int Y = (int)(p % H); p /= H;
         const int c = (int)(p % C);
         const int b = (int)(p / C);
-        const Lerp ly = src_index(Y, sy, h);
+        const Tap ly = src_tap(sy, Y, h);
         const float* r0 = src + (((int64_t)b * h + ly.i0) * w) * ld + c;
         const float* r1 = src + (((int64_t)b * h + ly.i1) * w) * ld + c;
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int X = min(xq * 4 + e, W - 1);
-            const Lerp lx = src_index(X, sx, w);
+            const Tap lx = src_tap(sx, X, w);
             o[e] = alpha * (ly.l0 * (lx.l0 * r0[(int64_t)lx.i0 * ld] + lx.l1 * r0[(int64_t)lx.i1 * ld]) +
                             ly.l1 * (lx.l0 * r1[(int64_t)lx.i0 * ld] + lx.l1 * r1[(int64_t)lx.i1 * ld]));
         }

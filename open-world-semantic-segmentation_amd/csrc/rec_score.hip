@@ -20,7 +20,6 @@
 namespace {
 
 constexpr int REC_TX = 16, REC_THREADS = 256, REC_MAXS = DML_REC_MAX_SCALES, REC_W = 4;
-constexpr int REC_MAXC = 32;       // head.hip's MAXC
 
 struct RecArgs {
     const void* f1[REC_MAXS];
@@ -29,22 +28,6 @@ struct RecArgs {
     float sy[REC_MAXS], sx[REC_MAXS];
     int n, C, Hq, Wq;
 };
-
-// PyTorch area_pixel_compute_source_index, align_corners = False (pool_resize.hip's src_index)
-struct RecLerp {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ RecLerp rec_src_index(int dst, float scale, int in) {
-    float s = scale * ((float)dst + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    RecLerp r;
-    r.i0 = min((int)s, in - 1);
-    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-    r.l1 = s - (float)r.i0;
-    r.l0 = 1.f - r.l1;
-    return r;
-}
 
 // W consecutive channels as floats: 16 bytes of fp32 or 8 bytes of bf16 for W = 4, one element for W = 1
 template <typename T, int W> struct RecLoad;
@@ -75,7 +58,7 @@ __device__ __forceinline__ void rec_walk(const RecArgs& a, int b, int y, int x0,
     for (int s = 0; s < NS; ++s) {
         ja[s] = jb[s] = -1;
         if (s < a.n) {
-            const RecLerp ly = rec_src_index(y, a.sy[s], a.h[s]);
+            const Tap ly = src_tap(a.sy[s], y, a.h[s]);
             ly0[s] = ly.l0; ly1[s] = ly.l1;
             ro0[s] = ((b * a.h[s] + ly.i0) * a.w[s]) * a.ld[s];
             ro1[s] = ((b * a.h[s] + ly.i1) * a.w[s]) * a.ld[s];
@@ -88,7 +71,7 @@ __device__ __forceinline__ void rec_walk(const RecArgs& a, int b, int y, int x0,
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             if (s < a.n) {
-                const RecLerp lx = rec_src_index(x0 + p, a.sx[s], a.w[s]);
+                const Tap lx = src_tap(a.sx[s], x0 + p, a.w[s]);
                 const int ld = a.ld[s];
                 const T* base[2] = {static_cast<const T*>(a.f1[s]) + c, static_cast<const T*>(a.f2[s]) + c};
                 if (lx.i0 != ja[s]) {
@@ -206,15 +189,13 @@ __global__ __launch_bounds__(256) void rec_confidence_kernel(const float* __rest
             }
         }
         const float msp = prob_logit ? m : 1.f / sum;
-        const RecLerp ly = rec_src_index(Y, sy, Hq), lx = rec_src_index(X, sx, Wq);
+        const Tap ly = src_tap(sy, Y, Hq), lx = src_tap(sx, X, Wq);
         const float* c0 = cosv + ((int64_t)b * Hq + ly.i0) * Wq;
         const float* c1 = cosv + ((int64_t)b * Hq + ly.i1) * Wq;
         const float rec = ly.l0 * (lx.l0 * c0[lx.i0] + lx.l1 * c0[lx.i1]) + ly.l1 * (lx.l0 * c1[lx.i0] + lx.l1 * c1[lx.i1]);
         conf[i] = msp > threshold ? msp : rec;
     }
 }
-
-bool rec_aligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
 
 }  // namespace
 
@@ -233,7 +214,7 @@ extern "C" int dml_rec_cosine(const void* const* f1, const void* const* f2, cons
         a.f1[s] = f1[k]; a.f2[s] = f2[k];
         a.h[s] = h[k]; a.w[s] = w[k]; a.ld[s] = ld[k];
         a.sy[s] = (float)h[k] / (float)Hq; a.sx[s] = (float)w[k] / (float)Wq;
-        vec = vec && ld[k] % REC_W == 0 && rec_aligned(f1[k], REC_W * es) && rec_aligned(f2[k], REC_W * es);
+        vec = vec && ld[k] % REC_W == 0 && aligned_to(REC_W * es, f1[k], f2[k]);
     }
     a.n = n; a.C = C; a.Hq = Hq; a.Wq = Wq;
     const int nxs = (Wq + REC_TX - 1) / REC_TX;
@@ -263,7 +244,7 @@ extern "C" int dml_rec_confidence(const float* scores, const float* cosv, float*
                                   int k_first, float threshold, int prob_logit, void* stream) {
     if (!scores || !cosv || !conf || B <= 0 || K <= 0 || H <= 0 || W <= 0 || Hq <= 0 || Wq <= 0 || k_first < 0 || k_first >= K)
         return DML_EINVAL;
-    if (K - k_first > REC_MAXC) return DML_EINVAL;
+    if (K - k_first > MAXC) return DML_EINVAL;
     if ((int64_t)H * W > (1ll << 40) / B || (int64_t)B * Hq * Wq > (1ll << 40)) return DML_EUNSUPPORTED;
     hipLaunchKernelGGL(rec_confidence_kernel, dim3(grid_for((int64_t)B * H * W, 256, 256 * 32)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), scores, cosv, conf, B, K, H, W, Hq, Wq, k_first, threshold, prob_logit,

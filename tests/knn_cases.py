@@ -17,7 +17,7 @@ A dropped or doubled neighbour moves a pixel by up to 1, about a thousand bars. 
 import numpy as np
 
 EPS32 = 2.0 ** -24
-MAXC = 32                       # csrc/knn_score.hip
+MAXC = 32                       # csrc/common.h
 MAX_NEIGHBOR_SIZE = 17
 CLAMP = 1e-8                    # ATen's cosine_similarity eps, applied to each vector's norm on its own
 BAR_OPS = 256

@@ -43,9 +43,9 @@ import numpy as np
 import open_set_cases as OC
 
 EPS32 = OC.EPS32
-MAX_CLASSES = 32                # csrc/head.hip: MIX_MAXK
-REG_CLASSES = 16                # csrc/head.hip: MIX_KREG, up to which pass 1 keeps the logits in registers
-PASS1_GRID = {True: 512, False: 2048}     # csrc/head.hip: MIX_GRID_REG, MIX_GRID_REREAD -- workgroups per image at most
+MAX_CLASSES = 32                # csrc/common.h: MAXC
+REG_CLASSES = 16                # csrc/scores.hip: MIX_KREG, up to which pass 1 keeps the logits in registers
+PASS1_GRID = {True: 512, False: 2048}     # csrc/scores.hip: MIX_GRID_REG, MIX_GRID_REREAD -- workgroups per image at most
 KS = (2, 13, 16, 19, 32)
 PROBS = ("softmax", "logit")
 CLIPS = (400.0, 1000.0)

@@ -10,7 +10,7 @@ import numpy as np
 
 import open_set_cases as CS
 
-MAXN = 8                                      # csrc/head.hip: prototypes per launch
+MAXN = 8                                      # csrc/scores.hip: prototypes per launch
 RANDOM_NS = (1, 2, 3, 8)
 RANDOM_SHAPE = (2, 96, 160)
 ODD_SHAPES = ((3, 5, 7), (1, 1, 1))           # H W not a multiple of 4: the one-pixel-per-lane path

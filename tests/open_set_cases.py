@@ -9,7 +9,7 @@ import numpy as np
 EPS32 = 2.0 ** -24
 EPS64 = 2.0 ** -53
 FLT_MAX = np.float32(np.finfo(np.float32).max)
-MAXC = 32                                     # csrc/head.hip: embedding dim supported by the head kernels
+MAXC = 32                                     # csrc/common.h: MAXC, embedding dim supported by the head kernels
 EXCLUDE_CAP = 1e-3                            # share of pixels whose fp64 decision margin may lie below the fp32 bound
 
 

@@ -11,7 +11,7 @@ guard regions of 0xAA bytes, each longer than a row of the output, which must be
 requested (NULL) cannot be written at all.  Each float check prints "MEASURE <what> err=<error> bar=<its bar>" for the element that
 takes the largest share of its bar (run with -s to see the figures).
 
-DIST_NT_DEFAULT (non-temporal stores of logits and features) is a compile-time constant of head.hip: only the compiled variant of the
+DIST_NT_DEFAULT (non-temporal stores of logits and features) is a compile-time constant of common.h: only the compiled variant of the
 C = K = 16 kernels can be tested here.
 
 Measured on the MI355X (the whole file, 65 tests, takes about 4.5 s there; the slowest test, an above-the-cap case, 0.7 s), as the

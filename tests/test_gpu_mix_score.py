@@ -1,4 +1,4 @@
-"""GPU: the "EDS + MMSP" anomaly score -- dml_dissum_msp_score (csrc/head.hip) through the C ABI, through
+"""GPU: the "EDS + MMSP" anomaly score -- dml_dissum_msp_score (csrc/scores.hip) through the C ABI, through
 utils.dissum_msp_score and through the open-set driver's `--ood dissum_msp`.
 
 Every float comparison is against the float64 definition of tests/mix_cases.py on the same float32 inputs (proved to be the

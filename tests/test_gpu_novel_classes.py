@@ -1,5 +1,5 @@
 """GPU: several few-shot novel classes in one open-world pass -- dml_open_world_post, dml_novel_relabel_multi and
-dml_class_feature_sums (csrc/head.hip) through the C ABI and through utils.
+dml_class_feature_sums (csrc/scores.hip, csrc/eval_sums.hip) through the C ABI and through utils.
 
 Every comparison is against the float64 definitions of tests/novel_cases.py and tests/open_set_cases.py on the same
 float32 inputs (proved to be the reference's rules, without a GPU, by tests/test_novel_refs.py).  Predictions are compared

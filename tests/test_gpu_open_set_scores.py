@@ -1,5 +1,5 @@
 """GPU: the open-set scoring and metric kernels at their edges -- dml_argmax_msp, dml_dissum_score, dml_novel_relabel,
-dml_confusion_update, dml_class_feature_sum (csrc/head.hip) and dml_ood_measures (csrc/ood_measures.hip) through the C
+dml_confusion_update, dml_class_feature_sum (csrc/scores.hip, csrc/eval_sums.hip) and dml_ood_measures (csrc/ood_measures.hip) through the C
 ABI, and the Python wrappers where they hold logic.
 
 Every comparison is against the float64 definitions of tests/open_set_cases.py on the same float32 inputs (proved right on
