@@ -1000,6 +1000,56 @@ int dml_open_set_sweep(const float* conf, const int64_t* pred, const int64_t* la
                        const int64_t* out_labels, int n_out, int n_classes, int unknown_id, int64_t* cube, int64_t* open_pred,
                        int write_idx, void* stream);
 
+/* The per-class ECDF certainty score (the recipe the reference keeps commented at DeepLabV3Plus-Pytorch/main_embedding.py:106-113,
+ * 172-226,249-260 and test_embedding.py:155-163,361-364): fit, over calibration frames and per class, the empirical CDF E_cl of the
+ * distance sums of the pixels labelled and predicted cl; score conf(p) = sum_cl softmax_cl(p) * Certainty(E_cl(s(p))).  An ECDF is kept
+ * as a histogram over NB equal bins of [0, clip].  Definitions the three entry points share, each a float32 operation that
+ * numpy.float32 restates bit for bit (the library is built without fast-math, and nothing below can be contracted):
+ *   classes  k_first <= k < K, Kn = K - k_first (k_first = 1: --exclude_back without a copy)
+ *   s(p)     = -(((L_kfirst(p) + L_kfirst+1(p)) + ...) + L_K-1(p)) + 0.0: ascending k from 0.0f, one rounding per addition
+ *   inv_w    = (float)NB / clip, one division
+ *   bin(s)   = NB - 1 where s >= clip; 0 where s <= 0; otherwise min((int)(s * inv_w), NB - 1), one product, truncated.
+ *              A NaN s has no bin; +inf falls in NB - 1 and -inf in 0.
+ *   pred(p)  = the first k in the range whose L_k(p) is maximal (dml_argmax_msp's rule), counted from k_first
+ *
+ * dml_ecdf_collect: logits[B,K,H,W] fp32 (NCHW, contiguous), labels[B,H,W] int64, hist device int64[Kn][NB].  For every pixel with
+ * k_first <= label < K, label - k_first == pred and s not NaN: hist[label - k_first][bin(s)] += 1.  Every other pixel (255, -1, a class
+ * below k_first, a wrong prediction) is skipped.  The call accumulates onto what hist holds: one call per calibration frame builds the
+ * sample.  A workgroup counts in uint32 LDS cells sized by the actual Kn * NB and adds its non-zero cells with 64-bit integer atomics:
+ * exact, order-free, bitwise reproducible; no workspace, no host synchronisation.  16-byte loads (4 pixels per lane) when
+ * H W % 4 == 0 and logits and labels are 16-byte aligned, one pixel per lane otherwise; Kn <= 16 keeps a lane's planes in registers.
+ * DML_EINVAL: a NULL pointer, B, K, H, W <= 0, k_first < 0 or >= K, clip <= 0 or not finite, NB < 1.  DML_EUNSUPPORTED: Kn > 32,
+ * NB > 2048, Kn * NB > 32768 (128 KiB of LDS: 13 x 2048, 19 x 1024 and 32 x 1024 fit), B > 65535, B H W > 2^40, or an image so large
+ * that a workgroup's 32-bit cells could overflow (from about 2^41 / B pixels on).  DML_EALIGN: logits off 4 bytes, labels or hist off 8.
+ *
+ * dml_ecdf_table: hist as above, table device float[NB][Kp] (bin-major: one pixel's Kn certainties are one contiguous row), Kp a
+ * multiple of 4 and >= Kn, thresholds device float[Kn] (mode 1; may be NULL otherwise).  Per class cl, n_cl = sum_b hist[cl][b] and
+ *   E_cl[b] = (float)((double)(hist[cl][0] + ... + hist[cl][b]) / (double)n_cl)        (the inclusive prefix sum)
+ *   mode 0 (hard, main_embedding.py:107-109):    table[b][cl] = E_cl[b] > cut ? 1 : E_cl[b]
+ *   mode 1 (sigmoid, test_embedding.py:156-161): table[b][cl] = 1 / (1 + expf(-slope * (E_cl[b] - E_cl[bin(thresholds[cl])])))
+ *                                                 (a NaN threshold gives NaN)
+ *   mode 2:                                       table[b][cl] = E_cl[b]
+ * A class with n_cl = 0 has E_cl = 1 everywhere and, in every mode, the certainty 1: with no evidence its softmax weight passes
+ * through.  Columns Kn..Kp-1 are written as 0.  One launch, Kp workgroups.
+ * DML_EINVAL: a NULL hist or table, Kn < 1, NB < 1, clip <= 0 or not finite, Kp % 4 != 0, Kp < Kn, mode outside 0..2, mode 1 without
+ * thresholds.  DML_EUNSUPPORTED: Kn > 32 or NB > 2048.  DML_EALIGN: hist off 8 bytes, thresholds off 4, table off 16.
+ *
+ * dml_ecdf_score: conf[B,H,W] fp32, conf(p) = (sum_k e_k(p) table[bin(s(p))][k - k_first]) / (sum_k e_k(p)) with
+ * e_k(p) = expf(L_k(p) - max_k L_k(p)), both sums in ascending k: the softmax in the two-read form of dml_dissum_msp_score.  A NaN
+ * s gives a NaN conf, and so does an infinite maximum (exp(inf - inf), as in float64).  The logits are read from memory once (Kn <= 20 keeps them in registers, more re-reads them from cache); a
+ * table row is read as Kp / 4 16-byte vectors through the caches.  16-byte loads and stores of the maps when H W % 4 == 0 and logits
+ * and conf are 16-byte aligned, one pixel per lane otherwise.  No atomics, no workspace: bitwise reproducible, and image b of a batch
+ * equals the image alone.
+ * DML_EINVAL: a NULL pointer, B, K, H, W <= 0, k_first < 0 or >= K, Kp % 4 != 0, Kp < Kn, clip <= 0 or not finite, NB < 1.
+ * DML_EUNSUPPORTED: Kn > 32, NB > 2048, B > 65535 or B H W > 2^40.  DML_EALIGN: logits or conf off 4 bytes, table off 16 (its rows
+ * are vectors).  Nothing is launched when any of the three returns a code. */
+int dml_ecdf_collect(const float* logits, const int64_t* labels, int64_t* hist, int B, int K, int H, int W, int k_first, float clip,
+                     int NB, void* stream);
+int dml_ecdf_table(const int64_t* hist, float* table, const float* thresholds, int Kn, int Kp, int NB, float clip, int mode,
+                   float cut, float slope, void* stream);
+int dml_ecdf_score(const float* logits, const float* table, float* conf, int B, int K, int H, int W, int k_first, int Kp, float clip,
+                   int NB, void* stream);
+
 /* Few-shot prototype extraction (the recipe at test_embedding.py:413-425 of the reference: mean of features_out over
  * the pixels of one class): sums[c] (device double[C], zeroed by the call) = sum of feats[p][c] over pixels with
  * labels[p] == class_id, count (device uint64) = their number.  C <= 32. */

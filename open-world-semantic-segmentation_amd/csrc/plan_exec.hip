@@ -114,6 +114,9 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_upsample_nhwc_to_nchw),
     DML_ENTRY(dml_confusion_update),
     DML_ENTRY(dml_open_set_sweep),
+    DML_ENTRY(dml_ecdf_collect),
+    DML_ENTRY(dml_ecdf_table),
+    DML_ENTRY(dml_ecdf_score),
     DML_ENTRY(dml_class_feature_sum),
     DML_ENTRY(dml_class_feature_sums),
     DML_ENTRY(dml_label_encode),

@@ -21,6 +21,9 @@ DISTILL_PARTIALS = 2 * 2048   # floats of dml_distill_fwd's block_partials
 OPEN_SWEEP_SPAN = 2048        # pixels of one workgroup's pass in dml_open_set_sweep
 OPEN_SWEEP_MAX_BLOCKS = 512   # its largest grid: beyond SPAN * MAX_BLOCKS pixels a workgroup makes several passes
 OPEN_SWEEP_MAX_T, OPEN_SWEEP_MAX_CLASSES, OPEN_SWEEP_MAX_OUT = 12, 33, 8
+ECDF_THREADS = 1024           # lanes of a dml_ecdf_collect workgroup; a pass covers 1024 pixels, or 4096 with 16-byte loads
+ECDF_MAX_BLOCKS = 512         # its largest grid, all images together: beyond that a workgroup makes several passes
+ECDF_MAX_CLASSES, ECDF_MAX_BINS, ECDF_MAX_CELLS = 32, 2048, 32768
 
 
 def metric_work_doubles(K, C):
@@ -226,6 +229,9 @@ _PROTOS = {
     "dml_convert_dtype": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),
     "dml_confusion_update": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p]),
     "dml_open_set_sweep": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "dml_ecdf_collect": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    "dml_ecdf_table": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_p]),
+    "dml_ecdf_score": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dml_class_feature_sum": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_p, c_p, c_p]),
     "dml_class_feature_sums": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p]),
     "dml_ood_workspace_bytes": (c_i64, [c_i64]),

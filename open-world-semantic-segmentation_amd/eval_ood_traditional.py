@@ -17,7 +17,12 @@ reproduced; and :492-510: crf-gauss -- a dense CRF on the scores whose only pair
 and runs pydensecrf's lattice on one CPU thread, here each step is two 1-D blurs and a softmax on the device,
 utils.dense_crf_gauss, with the intended geometry (the reference passes (h, w) where DenseCRF2D takes (width, height)) and
 no copy for --exclude_back (the reference stops at setUnaryEnergy with it).  The other CRF variant, `crf`, is not offered:
-its bilateral kernel over the 13-channel scores needs a 15-dimensional lattice filter, which is not separable), then
+its bilateral kernel over the 13-channel scores needs a 15-dimensional lattice filter, which is not separable; and `ecdf`
+-- the calibrated score the reference keeps commented in DeepLabV3Plus-Pytorch/main_embedding.py:106-113,172-226,249-260 and
+test_embedding.py:155-163,361-364: a fit pass, `calibrate`, counts the distance sums of the correctly predicted pixels of
+known-class frames into one histogram per class on the device, and conf = sum_cl softmax_cl * Certainty(E_cl(distance sum))
+with those empirical CDFs, utils.EcdfCalibrator; the only confidence here that is not normalised per frame, so that a value
+means the same on every frame), then
 `eval_ood_measure`
 (:128-148) and the pixel accuracy / IoU meters (:548-556) -- all on the device; nothing but the three OOD numbers and
 the confusion counts per frame reaches the host.
@@ -27,6 +32,7 @@ normalises on the device, bit for bit the reference's ValDataset tensors), or `-
 """
 import argparse
 import ast
+import contextlib
 import os
 import time
 
@@ -45,6 +51,12 @@ MIX = {"threshold": 0.2, "slope": 50.0}
 # `--ood crf-gauss`: the reference's addPairwiseGaussian(sxy=3, compat=3) and inference(100) (:501,504); main() puts
 # --crf_sxy / --crf_compat / --crf_iters here
 CRF = {"sxy": 3.0, "compat": 3.0, "iters": 100}
+# `--ood ecdf`: the certainty of the reference's two commented `Certainty` bodies (DeepLabV3Plus-Pytorch/main_embedding.py:106-113:
+# hard, E if E <= 0.15 else 1; test_embedding.py:155-163: a sigmoid of slope 50 around the mixture threshold), on the driver's
+# `dissum` clip; main() puts --ecdf_mode / --ecdf_cut / --ecdf_slope / --ecdf_bins / --ecdf_clip here, and the calibration itself
+# (utils.EcdfCalibrator, from calibrate() or --ecdf_load) under "calibrator", set and put back by use_calibrator(): confidence() and
+# evaluate() keep their signatures
+ECDF = {"mode": "hard", "cut": 0.15, "slope": 50.0, "bins": 1024, "clip": 400.0, "calibrator": None}
 
 
 def resized_shapes(h, w):
@@ -58,7 +70,16 @@ def confidence(scores, ood, exclude_back=False, feats=None):
     """:275-340, :434-448, :492-530.  scores [1, K, H, W] on the device -> conf [H, W] on the device.  `knn` reads the
     embedding feats [1, C, H, W] instead of the scores (the reference's `ft1`), so --exclude_back does not touch it.
     `dissum_msp` takes its gate from MIX, `crf-gauss` its kernel width, strength and step count from CRF; both skip the
-    background class inside the kernel."""
+    background class inside the kernel.  `ecdf` is the calibrated score: sum_cl softmax_cl * Certainty(E_cl(distance sum)) with
+    the per-class ECDFs of ECDF["calibrator"] (utils.EcdfCalibrator, filled by calibrate()) and the certainty of ECDF; it is
+    not normalised per frame."""
+    if ood == "ecdf":
+        cal = ECDF["calibrator"]
+        if cal is None:
+            raise ValueError("--ood ecdf needs a calibration: `with use_calibrator(calibrate(...)):` or utils.EcdfCalibrator.load")
+        if cal.first_class != (1 if exclude_back else 0):
+            raise ValueError("the calibration starts at class %d: exclude_back does not match it" % cal.first_class)
+        return cal.score(scores, mode=ECDF["mode"], cut=ECDF["cut"], slope=ECDF["slope"])[0]
     if ood == "knn":
         if feats is None:
             raise ValueError("--ood knn scores the embedding: pass feats")
@@ -80,6 +101,37 @@ def confidence(scores, ood, exclude_back=False, feats=None):
     if ood == "background":
         return tmp[0, 0]
     raise NotImplementedError("--ood %s" % ood)
+
+
+@contextlib.contextmanager
+def use_calibrator(calibrator):
+    """`with use_calibrator(cal): evaluate(..., ood="ecdf")`: the calibration confidence() and evaluate() score with inside the block;
+    what was set before comes back on the way out, also after an exception, so that no device-holding object stays behind in
+    the module's settings"""
+    previous = ECDF["calibrator"]
+    ECDF["calibrator"] = calibrator
+    try:
+        yield calibrator
+    finally:
+        ECDF["calibrator"] = previous
+
+
+def calibrate(segmentation_module, frames, num_known, exclude_back=False, max_frames=0, calibrator=None):
+    """The fit pass of `--ood ecdf` (the collection loop the reference keeps commented at main_embedding.py:177-197, without its
+    1-in-500 subsampling): frames as evaluate() takes them, known-class frames by intent; each goes through the same multi-scale
+    forward and every pixel whose label equals its prediction is counted into the calibrator's per-class histogram on the
+    device.  max_frames caps the frames read (0: all).  -> utils.EcdfCalibrator"""
+    cal = calibrator
+    for i, (imgs, seg_label) in enumerate(frames):
+        if max_frames and i >= max_frames:
+            break
+        scores, _ = models.evaluate_multiscale(segmentation_module, imgs, tuple(seg_label.shape))
+        if cal is None:
+            cal = utils.EcdfCalibrator(scores.shape[1], ECDF["clip"], ECDF["bins"], first_class=1 if exclude_back else 0)
+        cal.update(scores, seg_label[None])
+    if cal is None:
+        cal = utils.EcdfCalibrator(num_known, ECDF["clip"], ECDF["bins"], first_class=1 if exclude_back else 0)
+    return cal
 
 
 def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_back=False, open_set_thresholds=None):
@@ -141,6 +193,7 @@ def known_class_iou(seg_metrics, known):
 CFG_DEFAULTS = {
     "DATASET.root_dataset": "./data/",
     "DATASET.list_val": "./data/validation.odgt",
+    "DATASET.list_calib": "./data/training.odgt",       # the reference's DATASET.list_train: known classes only
     "DATASET.num_class": 13,
     "DATASET.imgSizes": IMG_SIZES,
     "DATASET.imgMaxSize": IMG_MAX_SIZE,
@@ -185,7 +238,21 @@ def load_cfg(cfg_file, overrides):
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--ood", default="dissum", choices=["msp", "maxlogit", "dissum", "background", "knn",
-                                                           "dissum_msp", "crf-gauss"])
+                                                           "dissum_msp", "crf-gauss", "ecdf"])
+    p.add_argument("--ecdf_mode", default=ECDF["mode"], choices=["hard", "sigmoid"],
+                   help="--ood ecdf: the certainty of an ECDF value E -- hard: E if E <= --ecdf_cut else 1; sigmoid: "
+                        "1 / (1 + exp(-ecdf_slope (E - E(threshold)))) around each class's Gaussian-mixture threshold")
+    p.add_argument("--ecdf_cut", type=float, default=ECDF["cut"], help="--ood ecdf: the hard mode's cut (the reference's 0.15)")
+    p.add_argument("--ecdf_slope", type=float, default=ECDF["slope"],
+                   help="--ood ecdf: the sigmoid mode's steepness (the reference's coefficient = 50)")
+    p.add_argument("--ecdf_bins", type=int, default=ECDF["bins"], help="--ood ecdf: bins of the per-class histograms, at most 2048")
+    p.add_argument("--ecdf_clip", type=float, default=ECDF["clip"],
+                   help="--ood ecdf: the distance sum at which the histograms end (the driver's dissum clip)")
+    p.add_argument("--ecdf_calib", type=int, default=None, metavar="N",
+                   help="--ood ecdf: calibrate on N frames first (synthetic run: N generated frames; real-data run: the first N "
+                        "frames of DATASET.list_calib, 0 for all of them)")
+    p.add_argument("--ecdf_load", default="", metavar="FILE", help="--ood ecdf: read the calibration from FILE instead")
+    p.add_argument("--ecdf_save", default="", metavar="FILE", help="--ood ecdf: write the calibration to FILE")
     p.add_argument("--mix_threshold", type=float, default=MIX["threshold"],
                    help="--ood dissum_msp: the normalised distance sum at which the gate is 1/2 (the reference's 0.2)")
     p.add_argument("--mix_slope", type=float, default=MIX["slope"],
@@ -218,10 +285,40 @@ def build_parser():
     return p
 
 
+def check_ecdf_source(opts):
+    """`--ood ecdf` needs its calibration from somewhere: --ecdf_load FILE or --ecdf_calib N"""
+    if opts.ood == "ecdf" and not opts.ecdf_load and opts.ecdf_calib is None:
+        raise SystemExit("--ood ecdf needs a calibration: --ecdf_calib N (fit on N frames first) or --ecdf_load FILE")
+    if opts.ood == "ecdf" and not opts.ecdf_load and opts.synthetic and opts.ecdf_calib < 1:
+        raise SystemExit("--synthetic --ood ecdf generates its calibration frames: --ecdf_calib N with N >= 1")
+
+
+def ecdf_calibrator(seg, opts, frames, num_known):
+    """the calibrator of a `--ood ecdf` run: loaded from --ecdf_load, or fitted on `frames` (a callable, so that nothing is built
+    when the file is there); written to --ecdf_save when asked, and reported per class"""
+    if opts.ood != "ecdf":
+        return None
+    if opts.ecdf_load:
+        cal = utils.EcdfCalibrator.load(opts.ecdf_load)
+        want_first = 1 if opts.exclude_back else 0
+        if cal.num_classes != num_known or cal.first_class != want_first:
+            raise SystemExit("%s holds %d classes from class %d on; this run has %d from %d on"
+                             % (opts.ecdf_load, cal.num_classes, cal.first_class, num_known, want_first))
+        ECDF.update(bins=cal.nbins, clip=cal.clip)
+    else:
+        cal = calibrate(seg, frames(), num_known, opts.exclude_back, max_frames=opts.ecdf_calib)
+    if opts.ecdf_save:
+        cal.save(opts.ecdf_save)
+    print("ECDF calibration: %d pixels, per class %s" % (int(cal.counts().sum()), cal.counts().tolist()))
+    return cal
+
+
 def main():
     opts = build_parser().parse_args()
     MIX.update(threshold=opts.mix_threshold, slope=opts.mix_slope)
     CRF.update(sxy=opts.crf_sxy, compat=opts.crf_compat, iters=opts.crf_iters)
+    ECDF.update(mode=opts.ecdf_mode, cut=opts.ecdf_cut, slope=opts.ecdf_slope, bins=opts.ecdf_bins, clip=opts.ecdf_clip)
+    check_ecdf_source(opts)
     device = torch.device("cuda", opts.gpu)
     torch.cuda.set_device(device)
     torch.manual_seed(304)
@@ -252,7 +349,17 @@ def main():
             lab = coarse.repeat_interleave(32, 0).repeat_interleave(32, 1)[:opts.height, :opts.width].contiguous()
             yield imgs, lab.to(device)
 
-    r = evaluate(seg, frames(), 14, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
+    def calib_frames():
+        # known classes only, from a generator of its own: the evaluation frames are the same with and without --ood ecdf
+        gc = torch.Generator().manual_seed(11)
+        for _ in range(opts.ecdf_calib):
+            imgs = [torch.randn(1, 3, h, w, generator=gc).to(device) for h, w in shapes]
+            coarse = torch.randint(0, 13, ((opts.height + 31) // 32, (opts.width + 31) // 32), generator=gc)
+            lab = coarse.repeat_interleave(32, 0).repeat_interleave(32, 1)[:opts.height, :opts.width].contiguous()
+            yield imgs, lab.to(device)
+
+    with use_calibrator(ecdf_calibrator(seg, opts, calib_frames, num_class)):
+        r = evaluate(seg, frames(), 14, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])          # :587-589
     print("Mean IoU: %.4f, Accuracy: %.2f%%, Inference Time: %.4fs" % (r["seg"]["Mean IoU"], 100.0 * r["seg"]["Overall Acc"],
                                                                         r["sec_per_frame"]))
@@ -268,9 +375,17 @@ def run_dataset(seg, cfg, opts, num_class, device):
                                  padding_constant=cfg["DATASET.padding_constant"], workers=opts.workers or None,
                                  device=device)
     print("# samples: {}".format(len(reader)))
-    tic = time.perf_counter()
-    r = evaluate(seg, reader, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
-    wall = time.perf_counter() - tic
+
+    def calib_frames():
+        return StreetHazardsReader(cfg["DATASET.root_dataset"], cfg["DATASET.list_calib"],
+                                   img_sizes=tuple(cfg["DATASET.imgSizes"]), img_max_size=cfg["DATASET.imgMaxSize"],
+                                   padding_constant=cfg["DATASET.padding_constant"], workers=opts.workers or None, device=device,
+                                   max_sample=opts.ecdf_calib if opts.ecdf_calib else -1)
+
+    with use_calibrator(ecdf_calibrator(seg, opts, calib_frames, num_class)):
+        tic = time.perf_counter()
+        r = evaluate(seg, reader, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
+        wall = time.perf_counter() - tic
     for i, iou in enumerate(r["known_iou"]):
         print("class [{}], IoU: {:.4f}".format(i, iou))
     print("[Eval Summary]:")

@@ -152,6 +152,230 @@ def open_set_predict(conf: torch.Tensor, preds: torch.Tensor, threshold: float, 
     return out
 
 
+ECDF_MODES = {"hard": 0, "sigmoid": 1, "ecdf": 2}
+
+
+def _need_cuda_tensor(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError("%s must be a CUDA tensor: the ECDF score runs on the HIP path only (no CPU fallback)" % what)
+
+
+def ecdf_certainty_score(logits: torch.Tensor, table: torch.Tensor, clip: float, first_class: int = 0) -> torch.Tensor:
+    """conf [B, H, W] = sum_k softmax_k * table[bin(s)][k - first_class] over the classes first_class .. K - 1 of logits
+    [B, K, H, W] (fp32, CUDA), with s = -sum_k logit_k and bin() the NB equal bins of [0, clip] (dml_ecdf_score; the header has the
+    bitwise definition).  table [NB, Kp] fp32 is what EcdfCalibrator.table returns: the certainty of every (bin, class), Kp the
+    class count rounded up to a multiple of 4.  One launch, one read of the logits; a pixel whose s is NaN comes back NaN."""
+    _need_cuda_tensor(logits, "logits")
+    _need_cuda_tensor(table, "table")
+    if logits.dim() != 4 or table.dim() != 2:
+        raise ValueError("logits must be [B, K, H, W] and table [NB, Kp]")
+    if logits.dtype != torch.float32 or table.dtype != torch.float32:
+        raise TypeError("logits and table must be float32")
+    lib = _lib.load()
+    logits, table = logits.contiguous(), table.contiguous()
+    B, K, H, W = logits.shape
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+    _lib.check(lib.dml_ecdf_score(logits.data_ptr(), table.data_ptr(), conf.data_ptr(), B, K, H, W, int(first_class),
+                                  table.shape[1], float(clip), table.shape[0], _st(logits)), "dml_ecdf_score")
+    return conf
+
+
+def _em_two_gaussians(x, c, floor, tol=1e-9, max_steps=500):
+    """EM of a two-component 1-D Gaussian mixture on the points x with the weights c (float64, at least two c > 0), the variances
+    kept at or above `floor`.  Deterministic: the components start as the two halves of the sample split at its weighted median.
+    Stops when the log-likelihood gains less than tol * |log-likelihood| or after max_steps.
+    -> (pi [2], mu [2], var [2], trace: the log-likelihood before every M-step and of the returned parameters last)"""
+    N = c.sum()
+    cum = np.cumsum(c)
+    med = int(np.searchsorted(cum, 0.5 * N))
+    low = np.arange(x.size) <= med
+    if not c[~low].sum() > 0:                  # the median bin is the last occupied one: it goes to the upper half
+        low = np.arange(x.size) < med
+    pi, mu, var = np.empty(2), np.empty(2), np.empty(2)
+    for j, half in enumerate((low, ~low)):
+        wj = c[half].sum()
+        pi[j] = wj / N
+        mu[j] = (c[half] * x[half]).sum() / wj
+        var[j] = max((c[half] * (x[half] - mu[j]) ** 2).sum() / wj, floor)
+    trace, prev = [], None
+    for _ in range(max_steps):
+        with np.errstate(divide="ignore"):
+            logp = np.log(pi)[:, None] - 0.5 * np.log(2.0 * np.pi * var)[:, None] - (x[None] - mu[:, None]) ** 2 / (2.0 * var[:, None])
+        top = logp.max(axis=0)
+        lse = top + np.log(np.exp(logp - top).sum(axis=0))
+        ll = float((c * lse).sum())
+        trace.append(ll)
+        if prev is not None and ll - prev < tol * abs(prev):
+            break
+        prev = ll
+        r = np.exp(logp - lse) * c                                          # responsibilities times the counts
+        nj = r.sum(axis=1)
+        for j in range(2):
+            if nj[j] > 0.0:                                                 # a component that died keeps its place
+                mu[j] = (r[j] * x).sum() / nj[j]
+                var[j] = max((r[j] * (x - mu[j]) ** 2).sum() / nj[j], floor)
+        pi = nj / N
+    return pi, mu, var, trace
+
+
+def fit_gmm_thresholds(hist, clip: float) -> np.ndarray:
+    """The per-class threshold of the reference's commented recipe (main_embedding.py:209-219: GaussianMixture(n_components=2),
+    thre = mean - sqrt(variance) of the component with the smaller variance) from the histogram [Kn, NB] of EcdfCalibrator:
+    EM on the bin centres (b + 1/2) w, w = clip / NB, weighted by the counts -- a fit of a few kilobytes on the host, once per
+    calibration.  Deterministic where sklearn's k-means initialisation is not: see _em_two_gaussians; the variance floor is
+    w^2 / 12 (a bin's own spread) + 1e-6 (sklearn's reg_covar).  A class with fewer than two occupied bins gets its smallest
+    occupied bin centre, an empty class 0 -> float64 [Kn]."""
+    hist = np.asarray(hist, dtype=np.float64)
+    Kn, NB = hist.shape
+    w = float(clip) / NB
+    x = (np.arange(NB) + 0.5) * w
+    out = np.zeros(Kn)
+    for cl in range(Kn):
+        occ = np.flatnonzero(hist[cl] > 0)
+        if occ.size < 2:
+            out[cl] = x[occ[0]] if occ.size else 0.0
+            continue
+        _, mu, var, _ = _em_two_gaussians(x, hist[cl], w * w / 12.0 + 1e-6)
+        j = int(np.argmin(var))
+        out[cl] = mu[j] - np.sqrt(var[j])
+    return out
+
+
+class EcdfCalibrator:
+    """The calibrated certainty score the reference keeps commented (main_embedding.py:106-113,172-226,249-260;
+    test_embedding.py:155-163,361-364): per class, the empirical CDF of the distance sums s = -sum_k logit_k of the calibration
+    pixels that are labelled and predicted that class, then conf = sum_cl softmax_cl * Certainty(E_cl(s)).  Unlike the per-frame
+    min-max scores its value means the same on every frame.
+
+        cal = EcdfCalibrator(num_classes, clip=400.0)
+        for logits, labels in calibration_frames:          # CUDA tensors; every pixel counts, nothing is copied to the host
+            cal.update(logits, labels)
+        conf = cal.score(logits)                           # mode="hard": E if E <= cut else 1;  "sigmoid": around the GMM threshold
+        cal.save(path); cal = EcdfCalibrator.load(path)    # calibrate once, reuse
+
+    The ECDF is a histogram over `nbins` equal bins of [0, clip] (int64 [Kn, nbins] on the device, Kn = num_classes -
+    first_class, Kn * nbins <= 32768), exact and independent of the order of the frames.  first_class=1 is --exclude_back."""
+
+    def __init__(self, num_classes: int, clip: float, nbins: int = 1024, first_class: int = 0):
+        self.num_classes, self.clip, self.nbins, self.first_class = int(num_classes), float(clip), int(nbins), int(first_class)
+        kn = self.num_classes - self.first_class
+        if self.first_class < 0 or not 1 <= kn <= _lib.ECDF_MAX_CLASSES:
+            raise ValueError("between 1 and %d classes from first_class on, not %d" % (_lib.ECDF_MAX_CLASSES, kn))
+        if not 1 <= self.nbins <= _lib.ECDF_MAX_BINS or kn * self.nbins > _lib.ECDF_MAX_CELLS:
+            raise ValueError("nbins must be in 1 .. %d with classes x nbins <= %d" % (_lib.ECDF_MAX_BINS, _lib.ECDF_MAX_CELLS))
+        if not (self.clip > 0.0 and np.isfinite(self.clip)):
+            raise ValueError("clip must be positive and finite")
+        self.n_known = kn
+        self.hist = torch.zeros((kn, self.nbins), dtype=torch.int64)
+        self._invalidate()
+
+    def _invalidate(self):
+        """what is derived from the histogram: the table last built and the fitted thresholds"""
+        self._tables = {}
+        self._fitted = None
+
+    def _device(self, device=None):
+        if device is None:
+            device = self.hist.device if self.hist.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:              # "cuda" is the current device, not another one than cuda:0
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.hist.device != device:
+            self.hist = self.hist.to(device)
+            self._invalidate()
+        return device
+
+    def update(self, logits: torch.Tensor, labels: torch.Tensor):
+        """count the pixels of logits [B, K, H, W] (fp32) whose labels [B, H, W] (int64) equal their prediction (dml_ecdf_collect)"""
+        _need_cuda_tensor(logits, "logits")
+        _need_cuda_tensor(labels, "labels")
+        if logits.dtype != torch.float32 or labels.dtype != torch.int64:
+            raise TypeError("logits must be float32 and labels int64, not %s / %s" % (logits.dtype, labels.dtype))
+        if logits.dim() != 4 or logits.shape[1] != self.num_classes:
+            raise ValueError("logits must be [B, %d, H, W]" % self.num_classes)
+        B, K, H, W = logits.shape
+        if labels.numel() != B * H * W:
+            raise ValueError("labels must be [B, H, W]")
+        lib = _lib.load()
+        self._device(logits.device)
+        self._invalidate()
+        logits, labels = logits.contiguous(), labels.contiguous()
+        _lib.check(lib.dml_ecdf_collect(logits.data_ptr(), labels.data_ptr(), self.hist.data_ptr(), B, K, H, W, self.first_class,
+                                        self.clip, self.nbins, _st(logits)), "dml_ecdf_collect")
+
+    def counts(self) -> np.ndarray:
+        """the per-class sample sizes, int64 [Kn]"""
+        return self.hist.sum(dim=1).cpu().numpy()
+
+    def fit_thresholds(self) -> np.ndarray:
+        """fit_gmm_thresholds on the histogram: float64 [Kn], the `thresholds` of the sigmoid mode.  Fitted once per calibration:
+        the result is kept until the next update (one copy of the histogram to the host, which waits for the stream)"""
+        if self._fitted is None:
+            self._fitted = fit_gmm_thresholds(self.hist.cpu().numpy(), self.clip)
+        return self._fitted.copy()
+
+    def table(self, mode: str = "hard", cut: float = 0.15, slope: float = 50.0, thresholds=None, device=None) -> torch.Tensor:
+        """The certainty of every (bin, class) as a device tensor [nbins, Kp] fp32, Kp = Kn rounded up to a multiple of 4
+        (dml_ecdf_table).  mode "hard": E if E <= cut else 1 (main_embedding.py:107-109); "sigmoid": 1 / (1 + exp(-slope (E -
+        E(threshold_cl)))) (test_embedding.py:156-161), thresholds [Kn] or None for fit_thresholds(); "ecdf": E itself.  Kept
+        until the next update."""
+        if mode not in ECDF_MODES:
+            raise ValueError("mode must be one of %s, not %r" % (sorted(ECDF_MODES), mode))
+        device = self._device(device)
+        if mode == "sigmoid" and thresholds is None:
+            thresholds = self.fit_thresholds()
+        thr = None
+        if mode == "sigmoid":
+            thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+            if thr.size != self.n_known:
+                raise ValueError("one threshold per class: %d, not %d" % (self.n_known, thr.size))
+        key = (mode, float(cut), float(slope), None if thr is None else thr.tobytes())
+        if key not in self._tables:
+            lib = _lib.load()
+            kp = (self.n_known + 3) // 4 * 4
+            tab = torch.empty((self.nbins, kp), dtype=torch.float32, device=device)
+            tdev = None if thr is None else torch.from_numpy(thr).to(device)
+            _lib.check(lib.dml_ecdf_table(self.hist.data_ptr(), tab.data_ptr(), None if tdev is None else tdev.data_ptr(),
+                                          self.n_known, kp, self.nbins, self.clip, ECDF_MODES[mode], float(cut), float(slope),
+                                          torch.cuda.current_stream(device).cuda_stream), "dml_ecdf_table")
+            self._tables = {key: tab}
+        return self._tables[key]
+
+    def score(self, logits: torch.Tensor, mode: str = "hard", cut: float = 0.15, slope: float = 50.0, thresholds=None) -> torch.Tensor:
+        """conf [B, H, W] of logits [B, K, H, W]: ecdf_certainty_score with this calibration's table"""
+        _need_cuda_tensor(logits, "logits")
+        if logits.dim() != 4 or logits.shape[1] != self.num_classes:
+            raise ValueError("logits must be [B, %d, H, W]" % self.num_classes)
+        tab = self.table(mode, cut, slope, thresholds, device=logits.device)
+        return ecdf_certainty_score(logits, tab, self.clip, self.first_class)
+
+    def state_dict(self):
+        return {"hist": self.hist.detach().cpu().clone(), "num_classes": self.num_classes, "clip": self.clip, "nbins": self.nbins,
+                "first_class": self.first_class}
+
+    def load_state_dict(self, state):
+        hist = torch.as_tensor(state["hist"]).to(torch.int64)
+        want = (int(state["num_classes"]), float(state["clip"]), int(state["nbins"]), int(state["first_class"]))
+        if want != (self.num_classes, self.clip, self.nbins, self.first_class) or tuple(hist.shape) != (self.n_known, self.nbins):
+            raise ValueError("the state is of another calibration: %r" % (want,))
+        self.hist = hist.clone().to(self.hist.device)
+        self._invalidate()
+
+    def save(self, path):
+        """the int64 histogram and the constructor's arguments as one .npz (written to `path` as it is given)"""
+        with open(path, "wb") as f:
+            np.savez(f, hist=self.hist.cpu().numpy(), num_classes=np.int64(self.num_classes), clip=np.float64(self.clip),
+                     nbins=np.int64(self.nbins), first_class=np.int64(self.first_class))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            cal = cls(int(z["num_classes"]), float(z["clip"]), int(z["nbins"]), int(z["first_class"]))
+            cal.load_state_dict({"hist": z["hist"], "num_classes": cal.num_classes, "clip": cal.clip, "nbins": cal.nbins,
+                                 "first_class": cal.first_class})
+        return cal
+
+
 def _nhwc_pitch(t):
     """the pixel pitch, in elements, of a [B, h, w, C] tensor that is dense but for that pitch (a channel slice of a wider
     buffer), or None for any other layout; dimensions of size 1 do not count"""
