@@ -1,7 +1,8 @@
 // Which kernel takes a convolution descriptor, and with which tiling: validation and choice of dml_conv_igemm, dml_conv_stat_rows,
 // dml_conv_wgrad and dml_conv_wgrad_group as pure host code -- integer arithmetic on a descriptor, no HIP, no allocation, no
 // pointer dereferenced (pointers are looked at for nullness, alignment and equality only).  conv_igemm.hip fills the kernel
-// arguments from the descriptor plus the choice and switches over it; tests/tools/conv_choice_dump.cpp prints it without a GPU.
+// arguments from the descriptor plus the choice and switches over it (the wave-specialised kernel's switch is the launcher of
+// conv_ws.hip, declared in conv_device.h); tests/tools/conv_choice_dump.cpp prints it without a GPU.
 // The measurement notes beside each rule are the record of why the rule is what it is.
 #pragma once
 #include <cstdint>

@@ -28,7 +28,7 @@ quantisation's backward) and the fp32 sum is rounded again; the HIP plan sums th
 tensor and rounds once (DmlConvDesc.acc32) -- one rounding fewer per producer, i.e. the plan is the more exact of the two.
 
 Parity status: the underlying model is PINNED (see dmlnet_ref.py); the quantisation points restate DESIGN.md section 2
-and csrc/bn.hip / conv_igemm.hip of this repository -- they describe the implementation under test, not the reference,
+and csrc/bn.hip / conv_device.h (conv_epilogue) of this repository -- they describe the implementation under test, not the reference,
 which has no reduced-precision mode.
 """
 from __future__ import annotations

@@ -43,7 +43,7 @@ struct Args {
     int ntiles_m, ntiles_n;
 };
 
-// weight-tile row order of the product kernels (conv_igemm.hip frag_chan / b_row / b_rho, NT = 4)
+// weight-tile row order of the product kernels (conv_device.h frag_chan / b_row / b_rho, NT = 4)
 __device__ __forceinline__ int frag_chan(int i, int g) { return (i >> 1) * 32 + g * 8 + (i & 1) * 4; }
 __device__ __forceinline__ int b_row(int i, int rho) { return frag_chan(i, rho >> 2) + (rho & 3); }
 __device__ __forceinline__ int b_rho(int row) { return ((row >> 3) & 3) * 4 + (row & 3); }
