@@ -1074,6 +1074,43 @@ int dml_ood_measures(const float* conf, const int64_t* seg_label, const uint8_t*
                      const int64_t* out_labels, int n_out, double recall_level, void* work,
                      int64_t work_bytes, double* result, void* stream);
 
+/* The same three measures over all pixels of a DATASET at once (pooled), where dml_ood_measures sorts one frame and the drivers
+ * average per-frame figures: frames weigh by their anomaly area, a frame without an anomaly counts as negatives, one threshold serves
+ * the whole set.  A sort needs every key resident; what streams is a histogram of the confidence over NB equal bins of [lo, hi].
+ * state: device int64[2 * NB + 5] = hist[2][NB] (row 0: positives, the pixels whose label is one of out_labels; row 1: negatives), then
+ * n_nan, n_below, n_above, n_masked, n_frames.  Plain additive memory: zero it to start, and two states over disjoint frames add
+ * element-wise (which is how ranks combine them).
+ *
+ * dml_pooled_ood_update: one read of conf (fp32), seg_label (int64, compared as int64: ids below 0 and above 2^31 are fine) and the
+ * optional mask (uint8, 0 = skip) of n pixels; out_labels is a HOST array of 1 <= n_out <= 8 ids, read before the call returns.  Per
+ * pixel, in this order: mask 0 -> n_masked += 1 and nothing else; conf NaN -> n_nan += 1 and nothing else; otherwise n_below += 1 where
+ * conf < lo, n_above += 1 where conf > hi (strictly outside, the infinities included: the user's sign that the range is wrong) and
+ * hist[row][bin(conf)] += 1 with the bin bitwise defined in float32, one rounding per operation, nothing contracted:
+ *   inv_w = (float)NB / (hi - lo)
+ *   bin   = NB - 1 where conf >= hi; 0 where conf <= lo; otherwise min((int)((conf - lo) * inv_w), NB - 1), truncated
+ * so -0.0 bins as 0.0, +inf falls in NB - 1 and -inf in 0.  n_frames += 1 per call with n > 0.  A workgroup counts in 2 NB + 4 uint32 LDS
+ * cells and adds its non-zero cells with 64-bit integer atomics: exact, order-free, bitwise reproducible; no workspace, no host
+ * synchronisation.  DML_EINVAL: a NULL conf, seg_label, out_labels or state, n < 0, NB outside 1..8192, n_out outside 1..8, lo, hi or
+ * hi - lo (in float32) not finite, hi <= lo.  DML_EALIGN: conf off 4 bytes, seg_label or state off 8.  n == 0 returns 0 and touches
+ * nothing.  DML_EUNSUPPORTED from about 2^40 pixels in one call on (a workgroup's 32-bit cells; the grid is capped at 256 workgroups).
+ *
+ * dml_pooled_ood_finalize: one workgroup; result (device double[8]) = { AUROC, AUPR, FPR at recall_level, P, N, tie mass, cut-off bin,
+ * 0 }: the measures of anom_utils.get_measures on the quantised scores -bin.  With P_b, N_b the two rows, tp_b = P_0 + ... + P_b and
+ * fp_b likewise (a pixel is flagged when its bin <= b):
+ *   AUROC = (sum_b P_b (2 (N - fp_b) + N_b)) / (2 P N)      the numerator an exact 128-bit integer, rounded once
+ *   AUPR  = sum_{b: P_b > 0} (P_b / P) (tp_b / (tp_b + fp_b))   float64, in a fixed ascending order (each of 256 lanes sums its
+ *           ceil(NB / 256) consecutive bins in ascending b, then the 256 partial sums are added in ascending order): reproducible
+ *   FPR   = fp / N of the candidate whose recall tp / P is nearest recall_level (the higher recall on a tie); candidates are the bins
+ *           with P_b > 0: the highest of them with its own (tp_b = P, fp_b), every other with its tp_b and the negatives of the bins
+ *           strictly below the next higher such bin (anom_utils.py:58-66); the cut-off bin is the candidate's bin
+ *   tie mass T = (sum_b P_b N_b) / (P N): binning is monotone, so only pairs inside one bin can change order, and the unquantised
+ *           pooled AUROC lies in [AUROC - T / 2, AUROC + T / 2]
+ * P == 0 or N == 0: AUROC, AUPR, FPR and T are NaN, the cut-off bin -1, P and N as they are.  Exact up to 2^40 pixels.
+ * DML_EINVAL: a NULL pointer, NB outside 1..8192, a NaN recall_level.  DML_EALIGN: state or result off 8 bytes. */
+int dml_pooled_ood_update(const float* conf, const int64_t* seg_label, const uint8_t* mask, int64_t n, const int64_t* out_labels,
+                          int n_out, float lo, float hi, int NB, int64_t* state, void* stream);
+int dml_pooled_ood_finalize(const int64_t* state, int NB, double recall_level, double* result, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Native replay of a static launch list.  The reference dispatches one Python call per layer per step
  * (nn.Module.forward / autograd, network/utils.py:84-118, backbone/resnet.py:95-115); the drop-in's plan is a fixed

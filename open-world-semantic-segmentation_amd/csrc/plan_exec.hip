@@ -117,6 +117,8 @@ const Entry kEntries[] = {
     DML_ENTRY(dml_ecdf_collect),
     DML_ENTRY(dml_ecdf_table),
     DML_ENTRY(dml_ecdf_score),
+    DML_ENTRY(dml_pooled_ood_update),
+    DML_ENTRY(dml_pooled_ood_finalize),
     DML_ENTRY(dml_class_feature_sum),
     DML_ENTRY(dml_class_feature_sums),
     DML_ENTRY(dml_label_encode),

@@ -24,6 +24,9 @@ OPEN_SWEEP_MAX_T, OPEN_SWEEP_MAX_CLASSES, OPEN_SWEEP_MAX_OUT = 12, 33, 8
 ECDF_THREADS = 1024           # lanes of a dml_ecdf_collect workgroup; a pass covers 1024 pixels, or 4096 with 16-byte loads
 ECDF_MAX_BLOCKS = 512         # its largest grid, all images together: beyond that a workgroup makes several passes
 ECDF_MAX_CLASSES, ECDF_MAX_BINS, ECDF_MAX_CELLS = 32, 2048, 32768
+POOLED_OOD_SPAN = 2048        # pixels of one workgroup's pass in dml_pooled_ood_update
+POOLED_OOD_MAX_BLOCKS = 256   # its largest grid, one workgroup per CU: beyond SPAN * MAX_BLOCKS pixels a workgroup makes several passes
+POOLED_OOD_MAX_BINS, POOLED_OOD_MAX_OUT, POOLED_OOD_COUNTERS = 8192, 8, 5
 
 
 def metric_work_doubles(K, C):
@@ -236,7 +239,9 @@ _PROTOS = {
     "dml_class_feature_sums": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p]),
     "dml_ood_workspace_bytes": (c_i64, [c_i64]),
     "dml_ood_measures": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i, C.c_double, c_p, c_i64, c_p, c_p]),
-    "dml_aug_contrast_sum": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "dml_pooled_ood_update": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_i, c_p, c_p]),
+    "dml_pooled_ood_finalize": (c_i, [c_p, c_i, C.c_double, c_p, c_p]),
+    "dml_aug_contrast_sum":(c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dml_aug_apply": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
     "dml_aug_apply_encoded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f,
                                     c_p, c_p, c_p, c_p]),

@@ -60,8 +60,9 @@ def confidence(scores, cos, ood, exclude_back=False):
     raise NotImplementedError("--ood %s" % ood)
 
 
-def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_back=False):
-    """frames: iterable of (img_resized_list, img_resized_list_rec, seg_label int64 [H, W]) on the device."""
+def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_back=False, pooled=None):
+    """frames: iterable of (img_resized_list, img_resized_list_rec, seg_label int64 [H, W]) on the device.  pooled: an
+    anom_utils.PooledOodMeasures that is given every frame's `conf` and `seg_label` as well (results under "pooled")."""
     seg_metrics = metrics_mod.StreamSegMetrics(num_class)
     aurocs, auprs, fprs, times = [], [], [], []
     known = num_class
@@ -80,13 +81,18 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
         if res is not None:
             aurocs.append(res[0]); auprs.append(res[1]); fprs.append(res[2])
         seg_metrics.update(seg_label[None], pred)
+        if pooled is not None:
+            pooled.update(conf, seg_label)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - tic)
-    return {"auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
-            "aupr": float(np.mean(auprs)) if auprs else float("nan"),
-            "fpr": float(np.mean(fprs)) if fprs else float("nan"),
-            "seg": seg_metrics.get_results(), "sec_per_frame": float(np.mean(times[1:] or times)),
-            "known_iou": T.known_class_iou(seg_metrics, known)}
+    r = {"auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
+         "aupr": float(np.mean(auprs)) if auprs else float("nan"),
+         "fpr": float(np.mean(fprs)) if fprs else float("nan"),
+         "seg": seg_metrics.get_results(), "sec_per_frame": float(np.mean(times[1:] or times)),
+         "known_iou": T.known_class_iou(seg_metrics, known)}
+    if pooled is not None:
+        r["pooled"] = pooled.get_results()
+    return r
 
 
 def build_parser():
@@ -98,6 +104,7 @@ def build_parser():
                    help="--ood rec: the maximum of the scores themselves (the reference's statement; the gate never opens on "
                         "its negative distances) or of their softmax")
     p.add_argument("--exclude_back", action="store_true")
+    T.add_pooled_arguments(p)
     p.add_argument("--out_label", type=int, default=13, help="cfg.OOD.out_labels: the anomaly id of StreetHazards")
     p.add_argument("--num_images", type=int, default=4)
     p.add_argument("--height", type=int, default=720)
@@ -157,8 +164,11 @@ def main():
         run_dataset(seg, cfg, opts, num_class, device)
         return
     frames = synthetic_frames(opts.num_images, opts.height, opts.width, opts.out_label, device)
-    r = evaluate(seg, frames, 14, opts.ood, (opts.out_label,), opts.exclude_back)
+    pooled = T.make_pooled(opts, (opts.out_label,))
+    r = evaluate(seg, frames, 14, opts.ood, (opts.out_label,), opts.exclude_back, pooled=pooled)
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])          # :199
+    if pooled is not None:
+        T.print_pooled(r["pooled"], pooled, opts.pooled_curve)
     print("Mean IoU: %.4f, Accuracy: %.2f%%, Inference Time: %.4fs" % (r["seg"]["Mean IoU"], 100.0 * r["seg"]["Overall Acc"],
                                                                         r["sec_per_frame"]))
 
@@ -174,7 +184,8 @@ def run_dataset(seg, cfg, opts, num_class, device):
     print("# samples: {}".format(len(reader)))
     frames = ((imgs, imgs_rec, seg_label) for (imgs, seg_label), (imgs_rec, _) in zip(reader, reader_rec))
     tic = time.perf_counter()
-    r = evaluate(seg, frames, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back)
+    pooled = T.make_pooled(opts, (opts.out_label,))
+    r = evaluate(seg, frames, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back, pooled=pooled)
     wall = time.perf_counter() - tic
     for i, iou in enumerate(r["known_iou"]):
         print("class [{}], IoU: {:.4f}".format(i, iou))
@@ -182,6 +193,8 @@ def run_dataset(seg, cfg, opts, num_class, device):
     print("Mean IoU: {:.4f}, Accuracy: {:.2f}%, Inference Time: {:.4f}s"
           .format(r["known_iou"].mean(), 100.0 * r["seg"]["Overall Acc"], r["sec_per_frame"]))
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])
+    if pooled is not None:
+        T.print_pooled(r["pooled"], pooled, opts.pooled_curve)
     print("Wall clock: {:.2f} frames/s ({} frames, {} decode workers per reader); model only: {:.2f} frames/s"
           .format(len(reader) / wall, len(reader), reader.workers, 1.0 / r["sec_per_frame"]))
     print("Evaluation Done!")

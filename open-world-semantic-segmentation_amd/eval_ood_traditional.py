@@ -25,7 +25,9 @@ with those empirical CDFs, utils.EcdfCalibrator; the only confidence here that i
 means the same on every frame), then
 `eval_ood_measure`
 (:128-148) and the pixel accuracy / IoU meters (:548-556) -- all on the device; nothing but the three OOD numbers and
-the confusion counts per frame reaches the host.
+the confusion counts per frame reaches the host.  `--pooled` adds the same three measures over all pixels of the run at once
+(anom_utils.PooledOodMeasures: every frame's confidence and label streamed into one histogram on the device) and the confidence
+threshold that reaches the recall level, beside the means of the per-frame figures.
 Data: a StreetHazards-layout tree from disk (the reference's command line: `--cfg FILE`, `--gpu`, `--ood`,
 `--exclude_back` and trailing `KEY VALUE` overrides; datasets/streethazards.py decodes on host threads and resizes /
 normalises on the device, bit for bit the reference's ValDataset tensors), or `--synthetic` frames.
@@ -57,6 +59,8 @@ CRF = {"sxy": 3.0, "compat": 3.0, "iters": 100}
 # (utils.EcdfCalibrator, from calibrate() or --ecdf_load) under "calibrator", set and put back by use_calibrator(): confidence() and
 # evaluate() keep their signatures
 ECDF = {"mode": "hard", "cut": 0.15, "slope": 50.0, "bins": 1024, "clip": 400.0, "calibrator": None}
+# `--pooled`: the anom_utils.PooledOodMeasures that evaluate() also feeds, set and put back by use_pooled(); None: no pooled measures
+POOLED = {"measures": None}
 
 
 def resized_shapes(h, w):
@@ -116,6 +120,19 @@ def use_calibrator(calibrator):
         ECDF["calibrator"] = previous
 
 
+@contextlib.contextmanager
+def use_pooled(pooled):
+    """`with use_pooled(anom_utils.PooledOodMeasures(...)): r = evaluate(...)`: the dataset-level accumulator evaluate() feeds
+    inside the block (None: none, and evaluate() does what it does without one); what was set before comes back on the way out.
+    It travels here, as the calibration does, because evaluate()'s positional signature is pinned."""
+    previous = POOLED["measures"]
+    POOLED["measures"] = pooled
+    try:
+        yield pooled
+    finally:
+        POOLED["measures"] = previous
+
+
 def calibrate(segmentation_module, frames, num_known, exclude_back=False, max_frames=0, calibrator=None):
     """The fit pass of `--ood ecdf` (the collection loop the reference keeps commented at main_embedding.py:177-197, without its
     1-in-500 subsampling): frames as evaluate() takes them, known-class frames by intent; each goes through the same multi-scale
@@ -137,7 +154,9 @@ def calibrate(segmentation_module, frames, num_known, exclude_back=False, max_fr
 def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_back=False, open_set_thresholds=None):
     """frames: iterable of (img_resized_list, seg_label int64 [H, W]) on the device.  open_set_thresholds: score the
     open-set prediction (:537-549, `pred[conf < thre] = out_labels[0]`) at each of them as well (:155-156,599-607) and
-    return the per-threshold results under "open_set"."""
+    return the per-threshold results under "open_set".  Inside `with use_pooled(p):` the anom_utils.PooledOodMeasures `p` is
+    given every frame's `conf` and `seg_label` as well, and its dataset-level results come back under "pooled"."""
+    pooled = POOLED["measures"]
     seg_metrics = metrics_mod.StreamSegMetrics(num_class)
     sweep = metrics_mod.OpenSetSweepMetrics(num_class, open_set_thresholds, out_labels[0], out_labels) \
         if open_set_thresholds else None
@@ -157,6 +176,8 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
         seg_metrics.update(seg_label[None], pred)
         if sweep is not None:
             sweep.update(seg_label, pred, conf)
+        if pooled is not None:
+            pooled.update(conf, seg_label)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - tic)
     r = {"auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
@@ -166,6 +187,8 @@ def evaluate(segmentation_module, frames, num_class, ood, out_labels, exclude_ba
          "known_iou": known_class_iou(seg_metrics, known)}
     if sweep is not None:
         r["open_set"] = sweep.get_results()
+    if pooled is not None:
+        r["pooled"] = pooled.get_results()
     return r
 
 
@@ -175,6 +198,47 @@ def print_open_set(results):
     print(metrics_mod.OpenSetSweepMetrics.to_str(results), end="")
     best = results[int(np.nanargmax([x["Mean IoU"] for x in results]))]
     print("Best open-set Mean IoU: %.4f at threshold %.4f" % (best["Mean IoU"], best["Threshold"]))
+
+
+def add_pooled_arguments(p):
+    """--pooled and its settings, shared with eval_ood_rec.py"""
+    p.add_argument("--pooled", action="store_true",
+                   help="also report AUROC / AUPR / FPR over all pixels of the run at once (anom_utils.PooledOodMeasures) beside "
+                        "the means of the per-frame figures, and the confidence threshold that reaches the recall level")
+    p.add_argument("--pooled_bins", type=int, default=4096, help="--pooled: bins of the confidence histogram, 1 .. 8192")
+    p.add_argument("--pooled_range", type=float, nargs=2, default=(0.0, 1.0), metavar=("LO", "HI"),
+                   help="--pooled: the confidence range the bins divide.  The default suits msp, dissum, dissum_msp, ecdf, "
+                        "crf-gauss and rec; maxlogit, background and knn are not confined to [0, 1] and need their own range")
+    p.add_argument("--pooled_curve", default="", metavar="FILE.npz",
+                   help="--pooled: write the cumulative curve (tp, fp, bin edges) to FILE.npz")
+
+
+def make_pooled(opts, out_labels):
+    """the accumulator of a --pooled run, None without the flag"""
+    if not opts.pooled:
+        return None
+    return anom_utils.PooledOodMeasures(out_labels, lo=opts.pooled_range[0], hi=opts.pooled_range[1], bins=opts.pooled_bins)
+
+
+def print_pooled(res, pooled, curve_file=""):
+    """the line after `mean auroc = ...`: the pooled measures, the AUROC interval binning leaves, the threshold at the recall
+    level and the pixels outside the range; then the curve file"""
+    if res is None:
+        c = pooled.counters()
+        print("pooled: no OOD pixel or only OOD pixels were counted (frames = %d, nan = %d, masked = %d)"
+              % (c["frames"], c["n_nan"], c["n_masked"]))
+    else:
+        print("pooled auroc = ", res["auroc"], "pooled aupr = ", res["aupr"], " pooled fpr = ", res["fpr"],
+              " auroc bounds = [%.9f, %.9f]" % res["auroc_bounds"],
+              " threshold at recall %g = %.9g" % (pooled.recall_level, res["threshold"]),
+              " below range = %d above range = %d nan = %d" % (res["n_below"], res["n_above"], res["n_nan"]))
+        outside, seen = res["n_below"] + res["n_above"], res["positives"] + res["negatives"]
+        if outside > 0.01 * seen:
+            print("WARNING: %d of %d pixels (%.2f%%) lie outside --pooled_range [%g, %g]; they were counted in its end bins"
+                  % (outside, seen, 100.0 * outside / seen, pooled.lo, pooled.hi))
+    if curve_file:
+        tp, fp, edges = pooled.curve()
+        np.savez(curve_file, tp=tp, fp=fp, edges=edges)
 
 
 def known_class_iou(seg_metrics, known):
@@ -268,6 +332,7 @@ def build_parser():
                    help="also score the open-set prediction (pixels whose confidence is below T become --out_label) at each "
                         "of these increasing thresholds, at most 12; the reference's sweep is 0.1 ... 0.9 on a confidence "
                         "normalised to [0, 1]")
+    add_pooled_arguments(p)
     p.add_argument("--out_label", type=int, default=13, help="cfg.OOD.out_labels: the anomaly id of StreetHazards")
     p.add_argument("--num_images", type=int, default=4)
     p.add_argument("--height", type=int, default=720)
@@ -358,9 +423,12 @@ def main():
             lab = coarse.repeat_interleave(32, 0).repeat_interleave(32, 1)[:opts.height, :opts.width].contiguous()
             yield imgs, lab.to(device)
 
-    with use_calibrator(ecdf_calibrator(seg, opts, calib_frames, num_class)):
+    pooled = make_pooled(opts, (opts.out_label,))
+    with use_calibrator(ecdf_calibrator(seg, opts, calib_frames, num_class)), use_pooled(pooled):
         r = evaluate(seg, frames(), 14, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])          # :587-589
+    if pooled is not None:
+        print_pooled(r["pooled"], pooled, opts.pooled_curve)
     print("Mean IoU: %.4f, Accuracy: %.2f%%, Inference Time: %.4fs" % (r["seg"]["Mean IoU"], 100.0 * r["seg"]["Overall Acc"],
                                                                         r["sec_per_frame"]))
     if "open_set" in r:
@@ -382,7 +450,8 @@ def run_dataset(seg, cfg, opts, num_class, device):
                                    padding_constant=cfg["DATASET.padding_constant"], workers=opts.workers or None, device=device,
                                    max_sample=opts.ecdf_calib if opts.ecdf_calib else -1)
 
-    with use_calibrator(ecdf_calibrator(seg, opts, calib_frames, num_class)):
+    pooled = make_pooled(opts, (opts.out_label,))
+    with use_calibrator(ecdf_calibrator(seg, opts, calib_frames, num_class)), use_pooled(pooled):
         tic = time.perf_counter()
         r = evaluate(seg, reader, num_class + 1, opts.ood, (opts.out_label,), opts.exclude_back, opts.open_set_thresholds)
         wall = time.perf_counter() - tic
@@ -392,6 +461,8 @@ def run_dataset(seg, cfg, opts, num_class, device):
     print("Mean IoU: {:.4f}, Accuracy: {:.2f}%, Inference Time: {:.4f}s"
           .format(r["known_iou"].mean(), 100.0 * r["seg"]["Overall Acc"], r["sec_per_frame"]))
     print("mean auroc = ", r["auroc"], "mean aupr = ", r["aupr"], " mean fpr = ", r["fpr"])
+    if pooled is not None:
+        print_pooled(r["pooled"], pooled, opts.pooled_curve)
     print("Wall clock: {:.2f} frames/s ({} frames, {} decode workers); model only: {:.2f} frames/s"
           .format(len(reader) / wall, len(reader), reader.workers, 1.0 / r["sec_per_frame"]))
     if "open_set" in r:
