@@ -8,12 +8,10 @@ training path for it is dead.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, switches
 from .engine import _PAD_CIN, Engine, Plan, _round_up
 
 
@@ -28,8 +26,7 @@ class PPMPlan(Plan):
         for mod in list(enc.modules()) + list(dec.modules()):
             if isinstance(mod, nn.BatchNorm2d) and mod.training:
                 raise NotImplementedError("a BatchNorm2d in train() mode inside an eval() model is not supported")
-        self.pre_prep, self.bn_eval = [], []
-        self.bn_eval_args = self.call(self.fwd, lib.dml_bn_eval_coeffs_table, 0, 0)
+        self.begin_forward(bn_eval_table=True)
         x_in = self.new(B, H, W, _PAD_CIN)
         self.images_args = self.call(self.fwd, lib.dml_pack_input, 0, x_in.ptr, B, 3, H, W, _PAD_CIN, self.dt)
 
@@ -85,17 +82,9 @@ class PPMPlan(Plan):
         if K != 13:
             # the reference hard-codes 13 centers (models.py:613-617); any other class count fails in its subtraction
             raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (13) at non-singleton dimension 3" % K)
-        cin = fin.in_channels
-        wpad, bpad = self.fbuf(Kp * cin, zero=True), self.fbuf(Kp, zero=True)
-
-        def stage(wpad=wpad, bpad=bpad, fin=fin, K=K, cin=cin):
-            wpad[:K * cin].copy_(fin.weight.detach().reshape(-1))
-            if fin.bias is not None:
-                bpad[:K].copy_(fin.bias.detach())
-        self.pre_prep.append(stage)
-        w_fin, _ = self.prep_weight(fin, cin, False, src_ptr=wpad.data_ptr(), N=Kp)
+        w_fin, _, bias_ptr = self.padded_final_conv(fin, K, Kp, False)
         emb = self.new(B, h, w, Kp, f32=True)
-        self.conv_fwd(ulast.z, fin, emb, w_fin, None, bias_ptr=bpad.data_ptr() if fin.bias is not None else None, N=Kp)
+        self.conv_fwd(ulast.z, fin, emb, w_fin, None, bias_ptr=bias_ptr, N=Kp)
         # distance to the 13 prototypes at 1/8 resolution (models.py:633-657), THEN the upsample to segSize (:659-668)
         protos = self.e.prototypes_padded(K, Kp)
         dist = self.new(B, h, w, Kp, f32=True)
@@ -103,10 +92,7 @@ class PPMPlan(Plan):
         self.up_scores = self.call(self.fwd, lib.dml_upsample_nhwc_to_nchw, dist.ptr, 0, B, h, w, Kp, K, 1, 1, 1.0, 0)
         self.up_feats = self.call(self.fwd, lib.dml_upsample_nhwc_to_nchw, emb.ptr, 0, B, h, w, Kp, K, 1, 1, 1.0, 0)
         self.K, self.Kp, self.heads = K, Kp, []
-        self.nbt_inc = None
-        arr = (_lib.BnEvalDesc * len(self.bn_eval))(*self.bn_eval)
-        self.bn_eval_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-        self.bn_eval_args[0], self.bn_eval_args[1] = self.bn_eval_table.data_ptr(), len(self.bn_eval)
+        self.end_forward()
 
 
 class PPMEngine(Engine):
@@ -142,7 +128,7 @@ class PPMEngine(Engine):
         Plan.run(plan.fwd, torch.cuda.current_stream(x.device).cuda_stream)
         return scores, feats
 
-    use_graphs = os.environ.get("DML_PPM_GRAPH", "1") == "1"
+    use_graphs = switches.ppm_graph()
 
     def _replay_body(self, plan, s):
         """The body of a scale (everything but the two upsample-accumulate launches) as one hipGraph: ~190 launches of a

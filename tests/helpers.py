@@ -138,7 +138,6 @@ def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float3
     Returns a PiecePlan with .run(inputs, grad_out) -> (output, input gradients); parameter gradients / running
     statistics land in the module (p.grad, buffers) exactly as in the full model."""
     import torch.nn as nn
-    from dmlnet import _lib
     from dmlnet import engine as E
 
     class _Holder(nn.Module):
@@ -149,19 +148,13 @@ def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float3
 
     class PiecePlan(E.Plan):
         def build(self):
-            self.bn_eval, self.pre_prep, self.nbt_inc = [], [], None
             self.to_backbone_ops, self.head_bwd_range = [], {}
-            # the head of Plan.build's forward in f16x2 training plans: zero every amax word, one launch for the plane scales of
-            # the residual-free BatchNorm outputs (its table is filled in once the forward is built)
-            self.h2_bound_tab, self.h2_bound_args = [], None
-            if self.h2_slots is not None and self.training:
-                self.call(self.fwd, self.lib.dml_fill_f32, self.h2_slots.data_ptr(), self.h2_slots.numel(), 0.0)
-                self.h2_bound_args = self.call(self.fwd, self.lib.dml_h2_bound_bn_table, 0, 0)
+            self.begin_forward(bn_eval_table=False)        # the frame of every forward, shared with Plan.build
             if kind == "block":
                 B, Cc, Hh, Ww = in_shapes[0]
                 self.inputs = [self.new(B, Hh, Ww, Cc)]
                 rec = self.block_fwd(self.inputs[0], module)
-                self._bound_table()
+                self.end_forward()
                 self.output = rec[3].z
                 self.grad_out = self.grad_of(self.output)
                 self.output.root.grad_init = True
@@ -174,19 +167,13 @@ def piece_plan(kind: str, module: torch.nn.Module, in_shapes, dtype=torch.float3
                 self.inputs = [low, out]
                 rec = self._head_fwd(module, low, out)
                 self.heads = [rec]
-                self._bound_table()
+                self.end_forward()
                 self.n_fwd = len(self.fwd) - 1              # without the final upsample + distance op (needs per-call outputs)
                 self.output = rec.emb
                 self._head_bwd(rec, low, out)
                 self.flush_wgrad()
                 self.grad_out = rec.de
                 self.skip = [r for r in (rec.fused_range, rec.unfused_range) if r is not None]
-
-        def _bound_table(self):
-            if self.h2_bound_args is not None and self.h2_bound_tab:
-                arr = (_lib.H2BoundDesc * len(self.h2_bound_tab))(*self.h2_bound_tab)
-                self.h2_bound_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-                self.h2_bound_args[0], self.h2_bound_args[1] = self.h2_bound_table.data_ptr(), len(self.h2_bound_tab)
 
         @staticmethod
         def _fill(act, t):          # NCHW cpu tensor -> the plan's NHWC buffer
