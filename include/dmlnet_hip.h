@@ -138,9 +138,11 @@ typedef struct DmlConvDesc {
      * f32_split == 1.  x_planes / w_planes: [2][...] fp16, the hi plane then the lo plane `*_plane_stride` elements further, the
      * activation planes with the geometry (pitch ldx) of `x`, the weight planes tile-major ([N / 64][K / 32][64][32] per plane);
      * x_unscale / w_unscale: device scalars 1 / s and 1 / t (dml_h2_split).  Shapes the planes kernel does not take (C % 32,
-     * N % 64, more than 32 taps, misaligned y) run the three-term split on x / w, which must therefore be valid as well --
-     * UNLESS the caller keeps the activation as planes only and says so by passing x == x_planes: such a launch returns
-     * DML_EUNSUPPORTED when the planes kernel cannot take it (never a fallback that would read the planes as floats). */
+     * N % 64, more than 32 taps, misaligned y, a data gradient with R S C < 64) run on x / w, which must therefore be valid as
+     * well: the three-term split where that kernel takes the shape (C % 32 == 0, at most 32 taps, N > 32), the exact fp32 MFMA
+     * otherwise (the 7 x 7 stem) -- UNLESS the caller keeps the activation as planes only and says so by passing
+     * x == x_planes: such a launch returns DML_EUNSUPPORTED when the planes kernel cannot take it (never a fallback that would
+     * read the planes as floats). */
     const void* x_planes;
     const void* w_planes;
     const float* x_unscale;
