@@ -32,9 +32,11 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__
             load_px<PX>(src + (int64_t)k * HW, v);
 #pragma unroll
             for (int p = 0; p < PX; ++p) {
-                // online log-sum-exp: one pass over the K planes
+                // online log-sum-exp: one pass over the K planes.  An equal value counts 1, not expf(v - mx): the same for finite
+                // ties (expf(0) is 1) and right for -inf while mx is still -inf.  +inf is outside the contract: one +inf plane gives an
+                // inf loss and two of them a finite denominator, where float64's inf - inf is NaN
                 if (v[p] > mx[p]) { den[p] = den[p] * expf(mx[p] - v[p]) + 1.f; mx[p] = v[p]; bi[p] = k; }
-                else den[p] += expf(v[p] - mx[p]);
+                else den[p] += v[p] == mx[p] ? 1.f : expf(v[p] - mx[p]);      // -inf while mx is -inf: exp(-inf + inf) is NaN
                 if ((int64_t)k == lab[p]) own[p] = v[p];
             }
         }
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
 #pragma unroll
             for (int p = 0; p < PX; ++p) {
                 if (v[p] > mx[p]) { den[p] = den[p] * expf(mx[p] - v[p]) + 1.f; mx[p] = v[p]; }
-                else den[p] += expf(v[p] - mx[p]);
+                else den[p] += v[p] == mx[p] ? 1.f : expf(v[p] - mx[p]);      // -inf while mx is -inf: exp(-inf + inf) is NaN
             }
         }
         float inv[PX];

@@ -21,10 +21,12 @@ template <int PX> __device__ __forceinline__ void focal_load_labels(const int64_
 
 // Online log-sum-exp that keeps the largest term out of the sum: sum_k exp(L_k) = exp(mx) * (1 + rest).  A pixel whose own
 // class dominates then has ce = log1p(rest) with rest tiny, where log(1 + rest) would have rounded to 0.
+// An equal value counts 1, not expf(v - mx): the same for finite ties and right for -inf while mx is still -inf; +inf logits are
+// outside the contract (two of them give a finite sum where float64's inf - inf is NaN).
 __device__ __forceinline__ void focal_lse_step(float v, float& mx, float& rest) {
 #pragma clang fp contract(off)
     if (v > mx) { rest = (rest + 1.f) * expf(mx - v); mx = v; }       // the first class: (0 + 1) * exp(-inf) = 0
-    else rest += expf(v - mx);
+    else rest += v == mx ? 1.f : expf(v - mx);                        // -inf while mx is -inf: exp(-inf + inf) is NaN
 }
 __device__ __forceinline__ float focal_ce(float mx, float own, float rest) {
 #pragma clang fp contract(off)

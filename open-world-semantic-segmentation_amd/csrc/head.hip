@@ -812,12 +812,21 @@ __global__ __launch_bounds__(256) void head_bwd_fused_c16_kernel(
                 const float wl = (x0 == q - 1 ? l0 : 0.f) + (x1 == q - 1 ? l1 : 0.f);
                 const float wc = (x0 == q ? l0 : 0.f) + (x1 == q ? l1 : 0.f);
                 const float wr = (x0 == q + 1 ? l0 : 0.f) + (x1 == q + 1 ? l1 : 0.f);
+                // a pixel reaches two of the three columns (one where x1 == x0): the third's weight is zero and is skipped, not
+                // multiplied -- 0 * NaN would carry a non-finite pixel into a column it does not interpolate into
+                float dfc[C];
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
-                    const float dfc = -2.f * (gs * f[c] - gm[c]);
-                    pl[c] += wl * dfc;
-                    pc[c] += wc * dfc;
-                    pr[c] += wr * dfc;
+                    dfc[c] = -2.f * (gs * f[c] - gm[c]);
+                    pc[c] += wc * dfc[c];
+                }
+                if (wl != 0.f) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) pl[c] += wl * dfc[c];
+                }
+                if (wr != 0.f) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) pr[c] += wr * dfc[c];
                 }
             }
         }

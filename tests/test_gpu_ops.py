@@ -915,7 +915,9 @@ def test_head_backward_fused_vs_plain_torch(lib, geom, dname, proto_kind):
     """dml_head_bwd_fused (loss gradient + distance-head gradient + transposed x4 upsample in one pass) against autograd
     through the reference's arithmetic (network/utils.py:88-118 + anomaly/models/models.py:42-78: interpolate ->
     distances -> CE/n + alpha VAR/n) on the CPU, and against the unfused kernel chain.  Tiles are 7 x 14 low-resolution
-    pixels: the geometries cover ragged tiles in both directions, single-tile maps and every border clamp."""
+    pixels: the geometries cover ragged tiles in both directions, single-tile maps and every border clamp.  Its edges (exact
+    inputs, one-row and one-column maps, guard bytes, NULL gout, n_images from sums[4], non-finite features) against float64:
+    tests/test_gpu_loss_edges.py."""
     from dmlnet import _lib as L
     from oracle import dmlnet_ref as O
     dt, tdt, _ = DT[dname]
@@ -1935,7 +1937,8 @@ def _loss_logits(name, B, K, Hh, Ww, regime):
 def test_dml_loss_against_fp64(lib, case, alpha, regime):
     """dml_loss_fwd -> dml_loss_finalize -> dml_loss_bwd (utils.DMLLoss, materialised gradient, gout = 0.5) against the oracle's
     DML loss in float64 autograd; then the same sums through the data-parallel branch of the C ABI (n_images = 0: the image count
-    read from sums[4] on the device).  G2's bars: loss 1e-5 relative, gradient 1e-5 of its max magnitude."""
+    read from sums[4] on the device).  G2's bars: loss 1e-5 relative, gradient 1e-5 of its max magnitude.  Per-element bars, K = 1,
+    ties, the grid caps and non-finite logits: tests/test_gpu_loss_edges.py."""
     import utils
     from dmlnet import _lib as L
     from oracle import dmlnet_ref as O
